@@ -14,10 +14,17 @@ gathered once over RCCL inside the timed region.  Prints ONE JSON line on rank 0
 
 The headline (`value`, `dtype`, `roofline`) is measured in the library's default arithmetic, which is
 fp32-equivalent (fp16x2: every fp32 operand, scaled by an exact power of two, as two fp16 planes to within 2^-24; three
-MFMA products per fp32 product, fp32 accumulation; see include/p2p_hip.h).  Outside the timed region rank 0 also (i) pushes one of the benched pairs -- through the
+MFMA products per fp32 product, fp32 accumulation; see include/p2p_hip.h).  A plain run stops there: set-up, warm-up,
+the K timed steps, the JSON line.  With `--full` (single-GPU runs), outside the timed region rank 0 also (i) pushes one
+of the benched pairs -- through the
 same batched calls -- and the CPU oracle and reports the differences (`parity`), (ii) times the other
 arithmetic modes for a few steps (`other_modes`, informational), (iii) times BASELINE configs[4] for a few steps
-(`other_configs.E`: 960x1280, ptmax 800 x panc 8 -- GPU legs only), (iv) times the oracle on the host (`cpu_baseline`).
+(`other_configs.E`: 960x1280, ptmax 800 x panc 8 -- GPU legs only), (iv) times the oracle on the host (`cpu_baseline`),
+(v) times the coarse stage alone (`coarse_stage_ms_per_pair`, `coarse_roofline`) and the end-to-end entry points (`e2e`).
+
+  --dump-outputs DIR   after the timed steps, rank 0 writes what the last timed step returned (the per-pair match arrays
+                       of fine_from_ticket, concatenated over the pairs of the step) as DIR/<name>.npy; the inputs and the
+                       proposal sampling are seeded, so two builds run with the same arguments can be compared array by array
 
   python bench.py --pairs 10000 [--gpus N]     BASELINE configs[3]: a stream of seeded pairs, pair i on rank i % N,
                                                 strong scaling (`scaling_efficiency` against rank 0 running alone)
@@ -88,17 +95,25 @@ def parse():
     ap.add_argument("--overlap", type=int, default=0,
                     help="1: coarse stage of step i+1 on a second stream beside the regress launch of step i; measured "
                          "neutral (444-446 vs 444-457 pairs/s: the regress launch stretches from 29.2 to 35.3 ms), so 0 is the default")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs outside the headline (parity vs the CPU oracle, other modes, config E, e2e, "
+                         "coarse-stage roofline, CPU baseline; the --no-* switches below drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the match arrays of the last timed step as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the in-run oracle check of a benched pair")
     ap.add_argument("--no-other-modes", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end estimate_matches timing")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the config-E leg of the default run")
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the config-E leg of a --full run")
     ap.add_argument("--pairs", type=int, default=0,
                     help="stream mode (BASELINE configs[3]): this many seeded pairs in total, sharded pair_id %% world, "
                          "generated on the device chunk by chunk; --steps / --warmup are ignored")
     ap.add_argument("--rendezvous-check", action="store_true",
                     help="only initialise the ranks (RCCL, or gloo without a GPU), all_gather their ranks, print them and exit")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(ngpus):
@@ -424,7 +439,12 @@ def resident_batches(cfg, rank, dev, nbatches, on_device=False):
         cpu_pairs = None
         pairs = [synthetic.make_correlated_pyramids_device(1000 + rank * 64 + i, H, W, dev) for i in range(nbatches * B)]
     else:
-        pairs = cpu_pairs = [synthetic.make_correlated_pyramids(1000 + rank * 64 + i, H, W) for i in range(nbatches * B)]
+        # each pair has its own seeded generator, so the pairs can be made side by side (torch releases the GIL): the
+        # same tensors as one after the other, in a fraction of the set-up time
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=max(1, min(8, usable_cores()))) as ex:
+            pairs = cpu_pairs = list(ex.map(lambda i: synthetic.make_correlated_pyramids(1000 + rank * 64 + i, H, W),
+                                            range(nbatches * B)))
     batches = []
     for k in range(nbatches):
         chunk = pairs[k * B:(k + 1) * B]
@@ -632,7 +652,8 @@ def _sync(dev):
 def timed_steps(run, nsteps, with_gather, rank, world, pairs_per_step, dev, dist):
     """The timed region of the weak-scaling contract: barrier + synchronize, `run(nsteps)` on this rank, the final gather
     of the match arrays (the only inter-GPU exchange of the path), barrier + synchronize.  -> elapsed (this rank's clock
-    over the whole region), local_elapsed (up to the end of this rank's own steps), the regress launch events, rows gathered."""
+    over the whole region), local_elapsed (up to the end of this rank's own steps), the regress launch events, rows gathered,
+    and this rank's per-step results."""
     from patch2pix_amd import ops
     from patch2pix_amd.gather import gather_matches, pack_results
 
@@ -655,7 +676,19 @@ def timed_steps(run, nsteps, with_gather, rank, world, pairs_per_step, dev, dist
     barrier()
     elapsed = time.perf_counter() - t0
     events, ops.regress_events = ops.regress_events, None
-    return {"elapsed": elapsed, "local_elapsed": local_elapsed, "events": events, "nrows": nrows}
+    return {"elapsed": elapsed, "local_elapsed": local_elapsed, "events": events, "nrows": nrows, "results": results}
+
+
+def dump_outputs(out_dir, step):
+    """--dump-outputs: the (fine, fine_scores, coarse) per-pair lists one step of fine_from_ticket returned, each
+    concatenated over the pairs of the step, plus the row count of every pair (to split them again)."""
+    fine, scores, coarse = step
+    arrays = {"fine": torch.cat(fine).float(), "fine_scores": torch.cat(scores).float(),
+              "coarse": torch.cat(coarse).double(),
+              "rows_per_pair": torch.tensor([float(f.shape[0]) for f in fine], dtype=torch.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def exchange_rank_stats(dist, dev, world, values):
@@ -714,6 +747,8 @@ def main():
     mode = net._weights()[1].mode
 
     if args.pairs:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the last step of the resident-batch run; the pair stream (--pairs) has none")
         out = stream_mode(args, net, cfg, mode, rank, world, dev, dist)
         if rank == 0:
             print(json.dumps(out), flush=True)
@@ -742,7 +777,13 @@ def main():
         # packing kernels and of the collectives (lazy code-object loads, RCCL channel set-up) costs tens of milliseconds
         if args.warmup > 0:
             timed(args.warmup, True)
-        elapsed, events, nrows, local_elapsed = timed(args.steps, True)
+        # the spin-up runs for a fixed time, not a fixed number of steps: reseed the proposal sampling (global numpy RNG,
+        # networks/utils.py) so that the timed steps, and what --dump-outputs writes, are the same from run to run
+        np.random.seed(1234 + rank)
+        t = timed_steps(run, args.steps, True, rank, world, B, dev, dist)
+        elapsed, events, nrows, local_elapsed = t["elapsed"], t["events"], t["nrows"], t["local_elapsed"]
+        last_step = t["results"][-1]
+        del t
     assert nrows == world * args.steps * B * PTMAX * cfg["panc"]
     # every rank's own numbers (weak scaling: each ran its own K steps): its rate up to the end of its own work, and the
     # roofline of its regress launches -- gathered so that rank 0 can print them; `elapsed` = the slowest rank's time
@@ -777,8 +818,11 @@ def main():
                      "torch_cpu_threads": torch.get_num_threads(), "usable_cores": usable_cores(),
                      "coarse_stages_enqueued_ahead": args.depth},
         }
-    # ---- outside the timed region (single-GPU runs only) ----
-    if rank == 0 and world == 1:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_step)
+    del last_step
+    # ---- --full: outside the timed region (single-GPU runs only) ----
+    if rank == 0 and world == 1 and args.full:
         out["coarse_stage_ms_per_pair"] = coarse_stage_ms(net, batches[0])
         try:
             out["coarse_roofline"] = coarse_roofline(net, batches[0], args.config)

@@ -221,8 +221,94 @@ def round3_cases(ref):
     case_real_pair(ref, "real_pair_3_contrast", "pair_3", 1024, contrast=4.0)
 
 
+def pin_feats(seed, h, w):
+    g = torch.Generator().manual_seed(seed)
+    return torch.relu(torch.randn(256, h, w, generator=g) + 0.2)
+
+
+def pin_fine_inputs(as_float, H=48, W=64, n=9):
+    p1 = synthetic.make_pyramid(21, H, W)
+    p2 = synthetic.make_pyramid(22, H, W)
+    g = torch.Generator().manual_seed(8)
+    m = torch.stack([torch.randint(0, W + 1, (n,), generator=g), torch.randint(0, H + 1, (n,), generator=g),
+                     torch.randint(0, W + 1, (n,), generator=g), torch.randint(0, H + 1, (n,), generator=g)], 1)
+    m[0] = torch.tensor([0, 0, W, H])          # corners: clamp paths
+    m[1] = torch.tensor([W, H, 0, 0])
+    if as_float:
+        m = m.float() + torch.rand(n, 4, generator=g) * 0.99
+        m[:, 0::2].clamp_(0, W)
+        m[:, 1::2].clamp_(0, H)
+    return p1, p2, m
+
+
+PIN_SD_SEED = 3
+
+
+def case_oracle_pins(ref, name="oracle_pins"):
+    """The reference's answers for tests/test_oracle_vs_reference.py, function by function, on the seeded inputs that
+    test builds (pin_feats / pin_fine_inputs above, the same recipes): outputs, the small inputs themselves, checksums
+    of the larger ones.  `python -m oracle.make_golden --pins`."""
+    sd = synthetic.make_state_dict(PIN_SD_SEED)
+    net = build_reference_net(sd, synthetic.default_regressor_config())
+    out = dict(sd_seed=PIN_SD_SEED)
+    with torch.no_grad():
+        fa, fb = pin_feats(0, 6, 8), pin_feats(1, 4, 10)
+        out["corr_input_checksum"] = checksum([fa, fb])
+        out["corr"] = np_(ref.modules.FeatCorrelation("4D")(ref.modules.L2Normalize(fa[None], 1),
+                                                             ref.modules.L2Normalize(fb[None], 1))[0, 0])
+        corr = torch.randint(0, 3, (8, 12, 6, 10), generator=torch.Generator().manual_seed(5)).float()
+        pooled = ref.modules.maxpool4d(corr[None, None], k_size=2)
+        out["maxpool_input"] = np_(corr)
+        out["maxpool_pooled"] = np_(pooled[0][0, 0])
+        out["maxpool_delta"] = np.stack([np_(r[0, 0]) for r in pooled[1:]])
+        x = torch.rand(5, 6, 7, 4, generator=torch.Generator().manual_seed(2))
+        out["mutual_input"] = np_(x)
+        out["mutual"] = np_(ref.ncn_model.MutualMatching(x[None, None])[0, 0])
+        x = torch.rand(6, 8, 5, 7, generator=torch.Generator().manual_seed(9))
+        out["conv4d_input"] = np_(x)
+        out["conv4d_layer1"] = np_(net.ncn.conv[0](x[None, None])[0])
+        out["consensus"] = np_(net.ncn(x[None, None])[0, 0])
+        fa, fb = pin_feats(10, 8, 12), pin_feats(11, 8, 12)
+        out["coarse_input_checksum"] = checksum([fa, fb])
+        rcorr, rdelta = net.forward_coarse_match(fa[None], fb[None], ksize=2)
+        rm, rs = net.cal_coarse_matches(rcorr, rdelta, ksize=2, upsample=8, center=True)
+        out["coarse_corr"] = np_(rcorr[0, 0])
+        out["coarse_delta"] = np.stack([np_(d[0, 0]) for d in rdelta])
+        out["coarse_matches"], out["coarse_scores"] = np_(rm[0]), np_(rs[0])
+        for mutual in (True, False):
+            rf, rfs = ref.utils.filter_coarse(rm, rs, 0.0, mutual)
+            out[f"filter_mutual{int(mutual)}"], out[f"filter_mutual{int(mutual)}_scores"] = np_(rf[0]), np_(rfs[0])
+        np.random.seed(4)
+        rf, _ = ref.utils.filter_coarse(rm, rs, 0.0, True, ptmax=50)
+        out["filter_ptmax50"] = np_(rf[0])
+        m = torch.randint(0, 100, (7, 4), generator=torch.Generator().manual_seed(6))
+        net.panc, net.pshift = 8, 8
+        out["anchors_input"] = np_(m)
+        out["anchors"] = np_(net.shift_to_anchors([m])[0])
+        net.panc = 1
+        for as_float in (False, True):
+            p1, p2, m = pin_fine_inputs(as_float)
+            out[f"fine{int(as_float)}_input_checksum"] = checksum(p1 + p2 + [m])
+            rm, rp = net.forward_fine_match([t[None] for t in p1], [t[None] for t in p2], [m], psize=16, ptype="center",
+                                            regressor=net.regress_mid)
+            out[f"fine{int(as_float)}_matches"], out[f"fine{int(as_float)}_scores"] = np_(rm[0]), np_(rp[0])
+        p1, p2 = synthetic.make_correlated_pyramids(31, 64, 96)
+        out["e2e_input_checksum"] = checksum(p1 + p2)
+        corr, delta = net.forward_coarse_match(p1[4][None], p2[4][None], ksize=2)
+        cm, cs = net.cal_coarse_matches(corr, delta, ksize=2, upsample=8, center=True)
+        cm, cs = ref.utils.filter_coarse(cm, cs, 0.0, True)
+        f1 = [t[None] for t in p1]
+        f2 = [t[None] for t in p2]
+        mid, _ = net.forward_fine_match(f1, f2, cm, 16, "center", net.regress_mid)
+        fine, fp = net.forward_fine_match(f1, f2, mid, 16, "center", net.regress_fine)
+        out["e2e_coarse"], out["e2e_mid"], out["e2e_fine"], out["e2e_fine_scores"] = np_(cm[0]), np_(mid[0]), np_(fine[0]), np_(fp[0])
+    np.savez_compressed(os.path.join(GOLDEN, name), **out)
+
+
 if __name__ == "__main__":
-    if "--r3" in sys.argv:
+    if "--pins" in sys.argv:
+        case_oracle_pins(load_reference())
+    elif "--r3" in sys.argv:
         round3_cases(load_reference())
     elif "--new" in sys.argv:
         os.makedirs(GOLDEN, exist_ok=True)

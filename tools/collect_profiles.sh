@@ -16,7 +16,7 @@ cd /tmp && export TMPDIR=/tmp
 [ -f $ROOT/profiles/kernel_times.json ] && [ ! -f $OUT/kernel_times.json ] && cp $ROOT/profiles/kernel_times.json $OUT/kernel_times.json
 # P2P_CONFIG=E profiles BASELINE configs[4] (960x1280, 2 pairs x 6400 proposals per step); files are tagged TAG_E_<mode>_*
 CFG=${P2P_CONFIG:-A}
-B="--no-cpu-baseline --no-parity --no-other-modes --no-e2e --no-other-configs --config $CFG"
+B="--full --no-cpu-baseline --no-parity --no-other-modes --no-e2e --no-other-configs --config $CFG"
 [ "$CFG" != "A" ] && TAG=${TAG}_${CFG}
 export P2P_CONFIG=$CFG
 for MODE in $MODES; do
