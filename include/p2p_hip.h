@@ -104,7 +104,7 @@ int p2p_regressor_get_mode(const p2p_regressor *reg);
 
 /* ---- coarse stage ---------------------------------------------------------------------------- */
 
-/* Workspace (bytes) p2p_coarse_forward needs for these sizes (per pair). */
+/* Workspace (bytes) p2p_coarse_forward needs for these sizes (per pair); ksize 1, 2 or 4. */
 size_t p2p_coarse_workspace_bytes(int channels, int hA, int wA, int hB, int wB, int ksize);
 
 /* Patch2Pix.forward_coarse_match -- reference networks/patch2pix.py:120-136:
@@ -115,7 +115,9 @@ size_t p2p_coarse_workspace_bytes(int channels, int hA, int wA, int hB, int wB, 
  *   corr4d_out [hA/k, wA/k, hB/k, wB/k]   device, fp32
  *   delta_out  same shape, uint8, value s = ((di*k+dj)*k+dk)*k+dl of the first maximum in the
  *              reference's slice order (modules.py:13-18); may be NULL; ignored when ksize == 1
- * ksize must be 1 or 2 (the reference default; other values -> P2P_EUNSUPPORTED).               */
+ * ksize must be 1, 2 (the reference's default in predict_*) or 4 (maxpool4d's own default; since version 103);
+ * other values -> P2P_EUNSUPPORTED (k^4 codes must fit the byte: 4 is the last value that does).  Feature map sides
+ * must be multiples of ksize (P2P_EINVAL otherwise).                                              */
 int p2p_coarse_forward(const float *featA, const float *featB, int channels, int hA, int wA, int hB, int wB,
                        int ksize, const p2p_ncn *ncn, float *corr4d_out, uint8_t *delta_out,
                        void *workspace, size_t workspace_bytes, p2p_stream_t stream);
@@ -124,7 +126,7 @@ int p2p_coarse_forward(const float *featA, const float *featB, int channels, int
  * networks/patch2pix.py:120-136): `batch` equally sized pairs, contiguous along the leading axis in all four
  * arrays, one launch per kernel for the whole batch.  The workspace must hold at least one pair
  * (p2p_coarse_workspace_bytes); with batch x that size all pairs are processed together, with less they are
- * processed in as many groups as fit.                                                             */
+ * processed in as many groups as fit.  ksize: 1, 2 or 4, as above.                                */
 int p2p_coarse_forward_batch(const float *featA, const float *featB, int batch, int channels, int hA, int wA, int hB,
                              int wB, int ksize, const p2p_ncn *ncn, float *corr4d_out, uint8_t *delta_out,
                              void *workspace, size_t workspace_bytes, p2p_stream_t stream);
@@ -138,7 +140,8 @@ int p2p_neigh_consensus_batch(const float *x, int batch, int hA, int wA, int hB,
                               void *workspace, size_t workspace_bytes, p2p_stream_t stream);
 
 /* Expand the packed relocalisation byte into the reference's four int64 tensors
- * (max_i, max_j, max_k, max_l of modules.py:24-28); `out` holds 4 consecutive planes of n int64. */
+ * (max_i, max_j, max_k, max_l of modules.py:24-28); `out` holds 4 consecutive planes of n int64.
+ * ksize: the one the byte was packed with (1, 2 or 4 from p2p_coarse_forward; code 255 = (3,3,3,3) at ksize 4). */
 int p2p_delta_unpack(const uint8_t *delta, size_t n, int ksize, int64_t *out, p2p_stream_t stream);
 
 /* Patch2Pix.cal_coarse_matches -- reference networks/patch2pix.py:340-375, i.e. corr_to_matches in
@@ -146,7 +149,7 @@ int p2p_delta_unpack(const uint8_t *delta, size_t n, int ksize, int64_t *out, p2
  * relocalisation with delta) concatenated B->A first then A->B, scaled to pixels:
  *   matches_out [nB + nA, 4] int64 = upsample * (xA,yA,xB,yB) (+ upsample/2 if center)
  *   scores_out  [nB + nA]    fp32                                    (nA = hA'*wA', nB = hB'*wB')
- * corr4d dims are the pooled ones; delta may be NULL (ksize 1).                                  */
+ * corr4d dims are the pooled ones; delta may be NULL (ksize 1); ksize 1, 2 or 4 (batch form alike). */
 int p2p_coarse_matches(const float *corr4d, const uint8_t *delta, int hA, int wA, int hB, int wB, int ksize,
                        int upsample, int center, int64_t *matches_out, float *scores_out, p2p_stream_t stream);
 

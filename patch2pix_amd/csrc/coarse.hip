@@ -7,7 +7,8 @@
 //                         features x 2^12 as two fp16 planes, in the 16 KB blocks the correlation GEMM copies into LDS by
 //                         LDS-DMA (piece q of row r at slot q ^ ((r >> 2) & 3): conflict-free fragment reads); positions
 //                         re-ordered cell-major so that the k^2 positions of one pooling cell are adjacent:
-//                         pos' = cell*k^2 + (i%k)*k + (j%k)
+//                         pos' = cell*k^2 + (i%k)*k + (j%k)  (k = 4: image A's rows permuted once more inside blocks of
+//                         32, prep_row_k4)
 //   P, Y, Y2 [nA'][nB']   fp32 pooled correlation volume viewed as a matrix (row = A cell, col = B cell); Y / Y2 =
 //                         the two branches of the consensus net (consensus.hip), summed by the kernels that read them
 //   delta   [nA'][nB']    uint8 argmax code s = ((di*k+dj)*k+dk)*k+dl
@@ -48,6 +49,10 @@ constexpr int PREP_P = 16;    // positions per work-group (300 groups at 60x80: 
 constexpr float CORR_FP16_SCALE = 4096.0f;
 // One launch for both images of every pair (blockIdx.y = image); the same launch resets the maxima keys of the mutual
 // matchings (nkeys words = -inf, then one word = 0: the float bits of max |X|, see mm_apply_kernel).
+// k = 4: a pooling cell is 16 GEMM rows (image A) x 16 GEMM columns (image B).  The rows of image A are permuted inside
+// every block of 32 (= two cells) so that cell e of the block sits on the rows (q & 3) + 8 (q >> 2) + 4 e, q = di * 4 + dj:
+// the rows whose products one half e of a wave holds in its 32x32 accumulator block, in register order (corr_pool_kernel<4>).
+__device__ __forceinline__ int prep_row_k4(int pp) { return (pp & ~31) + (pp & 3) + 2 * (pp & 12) + ((pp >> 2) & 4); }
 struct PrepArgs {
     const float *F[2];
     unsigned short *Fn[2];
@@ -59,6 +64,8 @@ struct PrepArgs {
     int nkeys;
     size_t sKeys;
 };
+// (PERM_A = the k = 4 instantiation: a template parameter, so that the kernel of k = 1, 2 is the code it was without it)
+template <bool PERM_A>
 __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     const int img = blockIdx.y;
     if (img == 0) {
@@ -66,6 +73,7 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
         if (i <= a.nkeys) a.keys[blockIdx.z * a.sKeys + i] = (i < a.nkeys) ? KEY_NEG_INF : 0;
     }
     const int h = a.h[img], w = a.w[img], C = a.C, k = a.k;
+    const bool perm = PERM_A && img == 0;
     if ((int)blockIdx.x * PREP_P >= h * w) return;
     const float *__restrict__ F = a.F[img] + blockIdx.z * a.sF[img];
     unsigned short *__restrict__ Fn = a.Fn[img] + blockIdx.z * a.sFn;
@@ -75,7 +83,8 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     if (((int)blockIdx.x + 1) * PREP_P >= h * w) {
         const int pad0 = h * w, pad1 = (pad0 + 127) & ~127, pieces = (C >> 5) * 2 * 4;      // 16-byte pieces per row
         for (int e = threadIdx.x; e < (pad1 - pad0) * pieces; e += 256) {
-            const int r = (pad0 + e / pieces) & 127, q = e % pieces, kc = q >> 3, pl = (q >> 2) & 1, piece = q & 3;
+            const int pr = pad0 + e / pieces;
+            const int r = (perm ? prep_row_k4(pr) : pr) & 127, q = e % pieces, kc = q >> 3, pl = (q >> 2) & 1, piece = q & 3;
             unsigned short *d = Fn + ((size_t)(pad0 >> 7) * (C >> 5) + kc) * (2 * 128 * 32) + pl * (128 * 32) + (r * 4 + piece) * 8;
             *(f32x4 *)d = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
@@ -117,7 +126,8 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
         const int pos = p0 + p;
         if (pos >= hw) break;
         const int i = pos / w, j = pos - i * w;
-        const int pp = ((i / k) * wc + (j / k)) * (k * k) + (i % k) * k + (j % k);
+        int pp = ((i / k) * wc + (j / k)) * (k * k) + (i % k) * k + (j % k);
+        if (perm) pp = prep_row_k4(pp);
         for (int c = tid; c < C; c += 256) {
             const float x = tile[c * (PREP_P + 1) + p] * inv[p] * CORR_FP16_SCALE;
             // block (pp / 128, c / 32): [plane][row pp % 128][piece (c / 8) % 4 at slot piece ^ ((row / 4) % 4)][c % 8]
@@ -299,7 +309,7 @@ __global__ __launch_bounds__(256, 2) void corr_pool_kernel(const unsigned short 
                     if (row < nA && col < nB) Pz[(size_t)row * nB + col] = acc[i][j][r] * inv;
                 }
             }
-    } else
+    } else if (KS == 2)
     // k = 2: a pooling cell is a 4x4 block: rows = (i,j) of A in regs 4g..4g+3, cols = (k,l) of B in 4 adjacent lanes.
     // First maximum in the order s = row_in_cell*4 + col_in_cell.  The exchange inside a quad of lanes is two DPP moves per
     // value (quad_perm; __shfl_xor goes through the LDS crossbar and is waited for: 64 of them were a third of a tile's
@@ -355,6 +365,56 @@ __global__ __launch_bounds__(256, 2) void corr_pool_kernel(const unsigned short 
                             if (Dl) Dl[at] = (uint8_t)ps[i][j][g];
                         }
                     }
+        }
+    }
+    if (KS == 4) {
+        // k = 4: a 32x32 accumulator block holds 2x2 cells.  prep_kernel put the 16 positions (di, dj) of an A cell on the
+        // rows of ONE half of the wave in register order (prep_row_k4), so register r of a lane is (di, dj) = (r >> 2, r & 3)
+        // of cell row `half`, and the 16 columns (dk, dl) of a B cell are the 16 lanes of a DPP row: the first maximum of the
+        // lane's own registers, then four DPP exchanges (lane ^ 1, ^ 2, ^ 7, ^ 8 span the row) under the total order
+        // "larger value, then smaller s" -- every lane of the row ends with the cell's result, lane 0 of it stores.
+        const int nAc = nA >> 4, nBc = nB >> 4;
+        const int crow0 = ((rowA0c + wr * 64) >> 4) + half, ccol0 = (rowB0c + wc * 64 + l31) >> 4;
+        float pbest[2][2];
+        int ps[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                float best = acc[i][j][0];
+                int s = 0;
+#pragma unroll
+                for (int r = 1; r < 16; ++r) {
+                    const float v = acc[i][j][r];
+                    if (v > best) { best = v; s = r; }
+                }
+                s = s * 16 + (lane & 15);
+#define CX_K4_STEP(XCHG)                                                                                               \
+                {                                                                                                      \
+                    const float ov = __uint_as_float(XCHG(__float_as_uint(best)));                                     \
+                    const int os = (int)XCHG((unsigned)s);                                                             \
+                    if (ov > best || (ov == best && os < s)) { best = ov; s = os; }                                    \
+                }
+                CX_K4_STEP(P2P_SWAP_ADJACENT)
+                CX_K4_STEP(P2P_SWAP_PAIRS)
+                CX_K4_STEP(P2P_MIRROR_HALF_ROW)
+                CX_K4_STEP(P2P_SWAP_HALF_ROWS)
+#undef CX_K4_STEP
+                pbest[i][j] = best * inv;
+                ps[i][j] = s;
+            }
+        if ((lane & 15) == 0) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int cr = crow0 + 2 * i, cc = ccol0 + 2 * j;
+                    if (cr < nAc && cc < nBc) {          // the padding rows of a tile are whole cells of zeros: never stored
+                        const unsigned at = (unsigned)(cr * nBc + cc);
+                        Pz[at] = pbest[i][j];
+                        if (dz) dz[at] = (uint8_t)ps[i][j];
+                    }
+                }
         }
     }
     if (!more) break;
@@ -672,7 +732,7 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
     hipStream_t stream = (hipStream_t)stream_;
     P2P_REQUIRE(featA && featB && ncn && corr4d_out && workspace, P2P_EINVAL, "p2p_coarse_forward: null argument");
     P2P_REQUIRE(batch >= 1 && batch <= 65535, P2P_EINVAL, "p2p_coarse_forward: batch %d out of range", batch);
-    P2P_REQUIRE(ksize == 1 || ksize == 2, P2P_EUNSUPPORTED, "p2p_coarse_forward: ksize %d not supported (1 or 2)", ksize);
+    P2P_REQUIRE(ksize == 1 || ksize == 2 || ksize == 4, P2P_EUNSUPPORTED, "p2p_coarse_forward: ksize %d not supported (1, 2 or 4)", ksize);
     P2P_REQUIRE(C > 0 && C % 32 == 0 && C <= 256, P2P_EUNSUPPORTED, "p2p_coarse_forward: channels %d (multiple of 32, <= 256)", C);
     P2P_REQUIRE(hA > 0 && wA > 0 && hB > 0 && wB > 0 && hA % ksize == 0 && wA % ksize == 0 && hB % ksize == 0 &&
                     wB % ksize == 0, P2P_EINVAL, "p2p_coarse_forward: feature map sizes must be positive multiples of ksize");
@@ -691,6 +751,7 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
     if (!attr_set_dev.done(dev)) {
         P2P_HIP_CHECK(hipFuncSetAttribute((const void *)corr_pool_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, CX_LDS));
         P2P_HIP_CHECK(hipFuncSetAttribute((const void *)corr_pool_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, CX_LDS));
+        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)corr_pool_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, CX_LDS));
         attr_set_dev.set(dev);
     }
 
@@ -714,7 +775,8 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
             pa.C = C; pa.k = ksize; pa.sFn = 2 * sWs;
             pa.keys = rkey1; pa.nkeys = nkeys; pa.sKeys = sWs;
             const int gp = std::max(ceil_div(std::max(nA, nB), PREP_P), ceil_div(nkeys + 1, 256));
-            hipLaunchKernelGGL(prep_kernel, dim3(gp, 2, nz), dim3(256), 0, stream, pa);
+            if (ksize == 4) hipLaunchKernelGGL(prep_kernel<true>, dim3(gp, 2, nz), dim3(256), 0, stream, pa);
+            else hipLaunchKernelGGL(prep_kernel<false>, dim3(gp, 2, nz), dim3(256), 0, stream, pa);
         }
         {
             const int gx = ceil_div(nB, CT), gy = ceil_div(nA, CT);
@@ -726,6 +788,9 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
             if (ksize == 1)
                 hipLaunchKernelGGL(corr_pool_kernel<1>, cgrid, dim3(256), CX_LDS, stream, fnA, fnB, nA, nB, C, P, (uint8_t *)nullptr,
                                    2 * sWs, sWs, (size_t)0, gx, gy, (int)ntiles, per_xcd);
+            else if (ksize == 4)
+                hipLaunchKernelGGL(corr_pool_kernel<4>, cgrid, dim3(256), CX_LDS, stream, fnA, fnB, nA, nB, C, P, dout, 2 * sWs, sWs,
+                                   nel, gx, gy, (int)ntiles, per_xcd);
             else
                 hipLaunchKernelGGL(corr_pool_kernel<2>, cgrid, dim3(256), CX_LDS, stream, fnA, fnB, nA, nB, C, P, dout, 2 * sWs, sWs,
                                    nel, gx, gy, (int)ntiles, per_xcd);

@@ -64,6 +64,22 @@ static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 #ifndef P2P_SWAP_PAIRS             // the same with the lane two further (lane ^ 2)
 #define P2P_SWAP_PAIRS(v) ((unsigned)__builtin_amdgcn_mov_dpp((int)(v), 0x4E, 0xF, 0xF, true))         /* quad_perm [2,3,0,1] */
 #endif
+// The two further steps of a reduction over a 16-lane DPP row (the k = 4 pooling epilogue): the same single DPP move on the
+// hardware; the kernel emulator of the test-suite has no DPP and takes the same lanes with __shfl_xor.
+#ifndef P2P_MIRROR_HALF_ROW        // the value of lane ^ 7 (the 8-lane halves of a row mirrored: quad 0 <-> quad 1, 2 <-> 3)
+#ifdef __HIPEMU__
+#define P2P_MIRROR_HALF_ROW(v) ((unsigned)__shfl_xor((int)(v), 7))
+#else
+#define P2P_MIRROR_HALF_ROW(v) ((unsigned)__builtin_amdgcn_mov_dpp((int)(v), 0x141, 0xF, 0xF, true))   /* row_half_mirror */
+#endif
+#endif
+#ifndef P2P_SWAP_HALF_ROWS         // the value of lane ^ 8 (the two 8-lane halves of a row exchanged)
+#ifdef __HIPEMU__
+#define P2P_SWAP_HALF_ROWS(v) ((unsigned)__shfl_xor((int)(v), 8))
+#else
+#define P2P_SWAP_HALF_ROWS(v) ((unsigned)__builtin_amdgcn_mov_dpp((int)(v), 0x128, 0xF, 0xF, true))    /* row_ror:8 */
+#endif
+#endif
 #ifndef P2P_LANE_ID                // lane index inside the wave, recomputed from the hardware (v_mbcnt) instead of kept in a register
 #define P2P_LANE_ID() ((int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)))
 #endif
