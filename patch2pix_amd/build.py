@@ -60,7 +60,8 @@ def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     import hashlib
     from concurrent.futures import ThreadPoolExecutor
-    headers = [d for d in _deps() if d.endswith(".h")]
+    # what a translation unit may include: the headers and the host-only sources that are no unit of their own (regress_api.hip)
+    headers = [d for d in _deps() if os.path.basename(d) not in SOURCES]
     # the compiler is part of an object's identity: after a ROCm / HIPCC switch stale objects must not be relinked
     try:
         compiler_id = hipcc + "\n" + subprocess.run([hipcc, "--version"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,

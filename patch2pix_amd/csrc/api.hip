@@ -1,4 +1,6 @@
-// Library-wide pieces of the C ABI: version and thread-local error string.
+// Library-wide pieces of the C ABI: version and thread-local error string.  This is also the translation unit of the host-only
+// API sources (included at the end), so that the list of units -- which the test-suite's CPU build repeats -- names kernels' files
+// and this one, whatever host code is split off them.
 #include "p2p_common.h"
 
 namespace p2p {
@@ -17,3 +19,5 @@ extern "C" int p2p_version(void) { return 103 | P2P_VERSION_EXPERIMENT; }
 extern "C" int p2p_version(void) { return 103; }
 #endif
 extern "C" const char *p2p_last_error(void) { return p2p::g_err; }
+
+#include "regress_api.hip"

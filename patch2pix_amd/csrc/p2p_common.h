@@ -133,24 +133,3 @@ struct p2p_ncn {
     unsigned char *wfused;   // both layers, both branches as fp16x2 MFMA fragments (consensus.hip), one device allocation
     int tile[3];             // forced (ta, tb, tc) of the fused kernel, 0 = automatic (p2p_ncn_set_tile: tests and sweeps)
 };
-
-struct p2p_regressor {
-    int device;        // the device the handle was created on: every later allocation (another mode's weight stream) goes there
-    float *dev;        // BatchNorm folds + FC layers (every mode)
-    float *dev_p, *dev_h, *dev_w;   // the convolution weights in the stream order of the f32 / fp16x2 / fp16x2w kernels; packed on
-                                    // the first selection of that mode (p2p_regressor_set_mode), null until then
-    std::vector<float> conv1_w, conv2_w, bn1s_host, bn2s_host;   // host copies the packings are built from
-    const float *wp1;  // f32: conv1 weights, MFMA-fragment order [8 waves][585 chunks][2][64 lanes][4]
-    const float *wp2;  //      conv2 weights,                    [8][576][2][64][4]
-    const float *wh1, *wh2;     // fp16x2: the same weights, scaled per output channel, split into two fp16 planes
-    const float *bn1s_h, *bn2s_h;   // fp16x2: folded BN scales times the inverse of those weight (and activation) scales
-    const float *ww2, *bn2s_w;      // fp16x2w: conv2 as Winograd-transformed filter blocks (regress_wino.hip) + its BN scale
-    const float *wh1_w, *bn1s_w;    // fp16x2w: conv1's fp16x2 stream and folded BN1 scale inside this mode's allocation (dev_w)
-    int mode;                   // P2P_REGRESS_F32 | P2P_REGRESS_FP16X2 | P2P_REGRESS_FP16X2W
-    const float *bn1s, *bn1b;   // folded BN scale/shift [512]
-    const float *bn2s, *bn2b;   // [512]
-    const float *fc1t, *fc1b, *bnf1s, *bnf1b;   // fc1 as [128][512][4]; [512]
-    const float *fc2t, *fc2b, *bnf2s, *bnf2b;   // fc2 as [128][256][4]; [256]
-    const float *fc3, *fc3b;                    // [5][256]; [5]
-    const float *fc1p, *fc2p;                   // fc1 / fc2 as B fragments of v_mfma_f32_16x16x4_f32: [k/16][n/16][lane 64][4]
-};

@@ -18,23 +18,10 @@
 //     time in exact consumption order: one global_load_dwordx4 per lane feeds four k-steps;
 //   * fp32 MFMA is bit-identical to an fma chain, so results match an fp32 CPU evaluation to
 //     round-off of the (fixed, documented) summation order: taps outer, channels inner.
+// This file: the kernel, its weight packer and its launcher (the handle and the C ABI: regress_api.hip).
 #include "regress_common.h"
 
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
 namespace p2p {
-
-constexpr int K1_CHUNKS_PER_TAP = 65;   // 1 (level-0 of both images, 6 ch padded to 8) + 2*(8+8+16)
-constexpr int K1_CHUNKS = 9 * K1_CHUNKS_PER_TAP;
-constexpr int K2_CHUNKS_PER_TAP = 64;   // 512 channels / 8
-constexpr int K2_CHUNKS = 9 * K2_CHUNKS_PER_TAP;
-constexpr int PF = 2;                   // weight prefetch distance (chunks); buffers are padded by PF chunks
-constexpr int WP1_FLOATS = 8 * (K1_CHUNKS + PF) * 2 * 64 * 4;
-constexpr int WP2_FLOATS = 8 * (K2_CHUNKS + PF) * 2 * 64 * 4;
-
 
 // LDS carve-up (floats)
 constexpr int TILE_L0 = 0, TILE_L1 = 768, TILE_L2 = 5952, TILE_L3 = 7552, TILE_IMG = 8704;
@@ -316,9 +303,7 @@ __global__ __launch_bounds__(NT, 2) void regress_kernel(RegressArgs args) {
     }
 }
 
-// --------------------------------------------------------------------------------------------------
-// host side: weight packing
-// --------------------------------------------------------------------------------------------------
+// ---- host side: the weight streams and the launch ------------------------------------------------
 
 // channel (0..517) of the concatenated [im1 259 | im2 259] regressor input for conv1 K index r (0..519)
 // inside one tap; -1 for the two padding slots.
@@ -331,250 +316,39 @@ static int conv1_channel_of(int r) {
     return img * 259 + 3 + cc;
 }
 
-static void fold_bn(const p2p_bn_params &bn, int n, float *scale, float *shift) {
-    for (int i = 0; i < n; ++i) {
-        const float inv = 1.0f / std::sqrt(bn.running_var[i] + 1e-5f);
-        const float a = bn.weight[i] * inv;
-        scale[i] = a;
-        shift[i] = bn.bias[i] - bn.running_mean[i] * a;
-    }
-}
-
-}  // namespace p2p
-
-using namespace p2p;
-
-// Arithmetic of the two convolutions: new regressors start in P2P_REGRESS_DEFAULT, p2p_regressor_set_mode selects another
-// mode per handle (the library reads no environment variables).  Only the weight stream of the mode in use is packed and
-// uploaded; another mode's is built on its first selection.
-static int upload(const std::vector<float> &h, float **dev, const char *what) {
-    *dev = nullptr;
-    P2P_HIP_CHECK(hipMalloc(dev, h.size() * sizeof(float)));
-    hipError_t e = hipMemcpy(*dev, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(*dev);
-        *dev = nullptr;
-        set_error("hipMemcpy of %s failed: %s", what, hipGetErrorString(e));
-        return P2P_EHIP;
-    }
-    return P2P_OK;
-}
-
-// pack + upload the convolution weights in the stream order of `mode`'s kernel (once per handle and mode)
-static int ensure_mode(p2p_regressor *r, int mode) {
-    auto al = [](size_t n) { return (n + 63) & ~size_t(63); };
-    const float *c1 = r->conv1_w.data(), *c2 = r->conv2_w.data();
-    if (mode == P2P_REGRESS_FP16X2W && !r->dev_w) {
-        // conv2 as Winograd filter blocks + conv1's fp16x2 stream (the same stream the direct mode runs, packed here on its own:
-        // the direct mode's conv2 stream -- 9.6 MB per regressor -- is neither packed nor uploaded for this mode)
-        const size_t ob2 = al(WW2_FLOATS), o1 = ob2 + 512, ob1 = o1 + al(WH1_FLOATS);
-        std::vector<float> h(ob1 + 512, 0.f);
-        std::vector<int> t1(512), t2(512);
-        pack_wino_weights(c2, &h[0], t2.data());
-        pack_h2_weights(c1, nullptr, &h[o1], nullptr, t1.data(), nullptr);
-        for (int n = 0; n < 512; ++n) {
-            h[ob2 + n] = std::ldexp(r->bn2s_host[n], -t2[n]);
-            h[ob1 + n] = std::ldexp(r->bn1s_host[n], -12 - t1[n]);      // conv1 accumulates 2^12 x 2^t1[n] x the true sum
+// wp1 [WP1_FLOATS], wp2 [WP2_FLOATS]: the PF chunks behind every wave's stream are not written (the caller zeroes them)
+void pack_f32_weights(const float *conv1_w, const float *conv2_w, float *wp1, float *wp2) {
+    // conv1: Wp1[w][kc][u][lane][q] = W1[n = 64w+32u+(lane&31)][channel(kidx)][tap],
+    //        kidx = 8*(kc % 65) + 2q + (lane>>5), tap = kc / 65
+    for (int w = 0; w < 8; ++w)
+        for (int kc = 0; kc < K1_CHUNKS; ++kc) {
+            const int tap = kc / K1_CHUNKS_PER_TAP, kin = kc % K1_CHUNKS_PER_TAP;
+            for (int u = 0; u < 2; ++u)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int q = 0; q < 4; ++q) {
+                        const int n = 64 * w + 32 * u + (lane & 31);
+                        const int ch = conv1_channel_of(8 * kin + 2 * q + (lane >> 5));
+                        const size_t dst = ((((size_t)w * (K1_CHUNKS + PF) + kc) * 2 + u) * 64 + lane) * 4 + q;
+                        wp1[dst] = (ch < 0) ? 0.f : conv1_w[((size_t)n * 518 + ch) * 9 + tap];
+                    }
         }
-        const int st = upload(h, &r->dev_w, "the Winograd filter blocks and conv1's stream");
-        if (st != P2P_OK) return st;
-        r->ww2 = r->dev_w; r->bn2s_w = r->dev_w + ob2; r->wh1_w = r->dev_w + o1; r->bn1s_w = r->dev_w + ob1;
-    } else if (mode == P2P_REGRESS_FP16X2 && !r->dev_h) {
-        const size_t o1 = 0, o2 = al(WH1_FLOATS), ob1 = o2 + al(WH2_FLOATS), ob2 = ob1 + 512;
-        std::vector<float> h(ob2 + 512, 0.f);
-        std::vector<int> t1(512), t2(512);
-        pack_h2_weights(c1, c2, &h[o1], &h[o2], t1.data(), t2.data());
-        // conv1 accumulates 2^12 (activations) x 2^t1[n] (weights) x the true sum, conv2 2^t2[n] x (the per-proposal scale of H,
-        // undone in the kernel) x the true sum: exact powers of two folded into the BatchNorm scales
-        for (int n = 0; n < 512; ++n) {
-            h[ob1 + n] = std::ldexp(r->bn1s_host[n], -12 - t1[n]);
-            h[ob2 + n] = std::ldexp(r->bn2s_host[n], -t2[n]);
+    // conv2: kidx = 8*(kc % 64) + 2q + (lane>>5) is the input channel, tap = kc / 64
+    for (int w = 0; w < 8; ++w)
+        for (int kc = 0; kc < K2_CHUNKS; ++kc) {
+            const int tap = kc / K2_CHUNKS_PER_TAP, kin = kc % K2_CHUNKS_PER_TAP;
+            for (int u = 0; u < 2; ++u)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int q = 0; q < 4; ++q) {
+                        const int n = 64 * w + 32 * u + (lane & 31);
+                        const int ch = 8 * kin + 2 * q + (lane >> 5);
+                        const size_t dst = ((((size_t)w * (K2_CHUNKS + PF) + kc) * 2 + u) * 64 + lane) * 4 + q;
+                        wp2[dst] = conv2_w[((size_t)n * 512 + ch) * 9 + tap];
+                    }
         }
-        const int st = upload(h, &r->dev_h, "the fp16x2 weight streams");
-        if (st != P2P_OK) return st;
-        r->wh1 = r->dev_h + o1; r->wh2 = r->dev_h + o2; r->bn1s_h = r->dev_h + ob1; r->bn2s_h = r->dev_h + ob2;
-    } else if (mode == P2P_REGRESS_F32 && !r->dev_p) {
-        const size_t o_wp1 = 0, o_wp2 = al(WP1_FLOATS);
-        std::vector<float> h(o_wp2 + al(WP2_FLOATS), 0.f);
-        // conv1: Wp1[w][kc][u][lane][q] = W1[n = 64w+32u+(lane&31)][channel(kidx)][tap],
-        //        kidx = 8*(kc % 65) + 2q + (lane>>5), tap = kc / 65
-        for (int w = 0; w < 8; ++w)
-            for (int kc = 0; kc < K1_CHUNKS; ++kc) {
-                const int tap = kc / K1_CHUNKS_PER_TAP, kin = kc % K1_CHUNKS_PER_TAP;
-                for (int u = 0; u < 2; ++u)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int q = 0; q < 4; ++q) {
-                            const int n = 64 * w + 32 * u + (lane & 31);
-                            const int ch = conv1_channel_of(8 * kin + 2 * q + (lane >> 5));
-                            const size_t dst = o_wp1 + ((((size_t)w * (K1_CHUNKS + PF) + kc) * 2 + u) * 64 + lane) * 4 + q;
-                            h[dst] = (ch < 0) ? 0.f : c1[((size_t)n * 518 + ch) * 9 + tap];
-                        }
-            }
-        // conv2: kidx = 8*(kc % 64) + 2q + (lane>>5) is the input channel, tap = kc / 64
-        for (int w = 0; w < 8; ++w)
-            for (int kc = 0; kc < K2_CHUNKS; ++kc) {
-                const int tap = kc / K2_CHUNKS_PER_TAP, kin = kc % K2_CHUNKS_PER_TAP;
-                for (int u = 0; u < 2; ++u)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int q = 0; q < 4; ++q) {
-                            const int n = 64 * w + 32 * u + (lane & 31);
-                            const int ch = 8 * kin + 2 * q + (lane >> 5);
-                            const size_t dst = o_wp2 + ((((size_t)w * (K2_CHUNKS + PF) + kc) * 2 + u) * 64 + lane) * 4 + q;
-                            h[dst] = c2[((size_t)n * 512 + ch) * 9 + tap];
-                        }
-            }
-        const int st = upload(h, &r->dev_p, "the f32 weight streams");
-        if (st != P2P_OK) return st;
-        r->wp1 = r->dev_p + o_wp1; r->wp2 = r->dev_p + o_wp2;
-    }
-    return P2P_OK;
 }
 
-extern "C" int p2p_regressor_set_mode(p2p_regressor *reg, int mode) {
-    P2P_REQUIRE(reg, P2P_EINVAL, "p2p_regressor_set_mode: null handle");
-    P2P_REQUIRE(mode == P2P_REGRESS_F32 || mode == P2P_REGRESS_FP16X2 || mode == P2P_REGRESS_FP16X2W, P2P_EINVAL,
-                "p2p_regressor_set_mode: unknown mode %d", mode);
-    // the weight stream of a mode is allocated on the HANDLE's device, whatever the caller's current device is
-    int cur = 0;
-    P2P_HIP_CHECK(hipGetDevice(&cur));
-    if (cur != reg->device) P2P_HIP_CHECK(hipSetDevice(reg->device));
-    const int st = ensure_mode(reg, mode);
-    if (cur != reg->device) P2P_HIP_CHECK(hipSetDevice(cur));
-    if (st != P2P_OK) return st;
-    reg->mode = mode;
-    return P2P_OK;
-}
-
-extern "C" int p2p_regressor_get_mode(const p2p_regressor *reg) { return reg ? reg->mode : P2P_EINVAL; }
-
-extern "C" int p2p_regressor_create(const p2p_regressor_params *p, p2p_regressor **out) {
-    P2P_REQUIRE(p && out, P2P_EINVAL, "p2p_regressor_create: null argument");
-    const float *const need[] = {p->conv1_w, p->conv2_w, p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->fc3_w, p->fc3_b,
-                                 p->bn1.weight, p->bn1.bias, p->bn1.running_mean, p->bn1.running_var,
-                                 p->bn2.weight, p->bn2.bias, p->bn2.running_mean, p->bn2.running_var,
-                                 p->bnf1.weight, p->bnf1.bias, p->bnf1.running_mean, p->bnf1.running_var,
-                                 p->bnf2.weight, p->bnf2.bias, p->bnf2.running_mean, p->bnf2.running_var};
-    for (const float *q : need) P2P_REQUIRE(q, P2P_EINVAL, "p2p_regressor_create: null weight pointer");
-
-    // everything but the convolution weights (which are packed per arithmetic mode, ensure_mode): one device allocation
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~size_t(63); return o; };
-    const size_t o_bn1s = take(512), o_bn1b = take(512), o_bn2s = take(512), o_bn2b = take(512);
-    const size_t o_fc1t = take(512 * 512), o_fc1b = take(512), o_bnf1s = take(512), o_bnf1b = take(512);
-    const size_t o_fc2t = take(256 * 512), o_fc2b = take(256), o_bnf2s = take(256), o_bnf2b = take(256);
-    const size_t o_fc3 = take(5 * 256), o_fc3b = take(8);
-    const size_t o_fc1p = take(512 * 512), o_fc2p = take(256 * 512);
-    std::vector<float> h(off, 0.f);
-    fold_bn(p->bn1, 512, &h[o_bn1s], &h[o_bn1b]);
-    fold_bn(p->bn2, 512, &h[o_bn2s], &h[o_bn2b]);
-    fold_bn(p->bnf1, 512, &h[o_bnf1s], &h[o_bnf1b]);
-    fold_bn(p->bnf2, 256, &h[o_bnf2s], &h[o_bnf2b]);
-    // fc weights as [k/4][out][4] so that a wave reads 1 KiB contiguous per step (per-proposal tail of the f32 kernel)
-    for (int o = 0; o < 512; ++o)
-        for (int k = 0; k < 512; ++k) h[o_fc1t + ((size_t)(k / 4) * 512 + o) * 4 + (k & 3)] = p->fc1_w[(size_t)o * 512 + k];
-    for (int o = 0; o < 256; ++o)
-        for (int k = 0; k < 512; ++k) h[o_fc2t + ((size_t)(k / 4) * 256 + o) * 4 + (k & 3)] = p->fc2_w[(size_t)o * 512 + k];
-    pack_fc_mfma(p->fc1_w, 512, &h[o_fc1p]);      // the same two layers as MFMA fragments (batched tail of the fp16x2 kernel)
-    pack_fc_mfma(p->fc2_w, 256, &h[o_fc2p]);
-    for (int i = 0; i < 512; ++i) h[o_fc1b + i] = p->fc1_b[i];
-    for (int i = 0; i < 256; ++i) h[o_fc2b + i] = p->fc2_b[i];
-    for (int i = 0; i < 5 * 256; ++i) h[o_fc3 + i] = p->fc3_w[i];
-    for (int i = 0; i < 5; ++i) h[o_fc3b + i] = p->fc3_b[i];
-
-    float *dev = nullptr;
-    int st = upload(h, &dev, "the regressor's BatchNorm / FC parameters");
-    if (st != P2P_OK) return st;
-    p2p_regressor *r = new p2p_regressor();
-    r->device = 0;
-    (void)hipGetDevice(&r->device);
-    r->dev = dev;
-    r->dev_p = r->dev_h = r->dev_w = nullptr;
-    r->ww2 = r->bn2s_w = r->wp1 = r->wp2 = r->wh1 = r->wh2 = r->bn1s_h = r->bn2s_h = r->wh1_w = r->bn1s_w = nullptr;
-    r->conv1_w.assign(p->conv1_w, p->conv1_w + (size_t)512 * 518 * 9);      // host copies: another mode's stream is packed on demand
-    r->conv2_w.assign(p->conv2_w, p->conv2_w + (size_t)512 * 512 * 9);
-    r->bn1s_host.assign(&h[o_bn1s], &h[o_bn1s] + 512);
-    r->bn2s_host.assign(&h[o_bn2s], &h[o_bn2s] + 512);
-    r->bn1s = dev + o_bn1s; r->bn1b = dev + o_bn1b; r->bn2s = dev + o_bn2s; r->bn2b = dev + o_bn2b;
-    r->fc1t = dev + o_fc1t; r->fc1b = dev + o_fc1b; r->bnf1s = dev + o_bnf1s; r->bnf1b = dev + o_bnf1b;
-    r->fc2t = dev + o_fc2t; r->fc2b = dev + o_fc2b; r->bnf2s = dev + o_bnf2s; r->bnf2b = dev + o_bnf2b;
-    r->fc3 = dev + o_fc3; r->fc3b = dev + o_fc3b;
-    r->fc1p = dev + o_fc1p; r->fc2p = dev + o_fc2p;
-    r->mode = P2P_REGRESS_DEFAULT;
-    st = ensure_mode(r, r->mode);
-    if (st != P2P_OK) {
-        p2p_regressor_destroy(r);
-        return st;
-    }
-    *out = r;
-    return P2P_OK;
-}
-
-extern "C" void p2p_regressor_destroy(p2p_regressor *reg) {
-    if (!reg) return;
-    (void)hipFree(reg->dev);
-    if (reg->dev_p) (void)hipFree(reg->dev_p);
-    if (reg->dev_h) (void)hipFree(reg->dev_h);
-    if (reg->dev_w) (void)hipFree(reg->dev_w);
-    delete reg;
-}
-
-static RegDev to_dev(const p2p_regressor *r) {
-    RegDev d;
-    d.ww2 = r->ww2; d.bn2s_w = r->bn2s_w; d.wp1 = r->wp1; d.wp2 = r->wp2; d.wh1 = r->wh1; d.wh2 = r->wh2;
-    d.bn1s_h = r->bn1s_h; d.bn2s_h = r->bn2s_h; d.bn1s = r->bn1s; d.bn1b = r->bn1b; d.bn2s = r->bn2s; d.bn2b = r->bn2b;
-    d.fc1t = r->fc1t; d.fc1b = r->fc1b; d.bnf1s = r->bnf1s; d.bnf1b = r->bnf1b;
-    d.fc2t = r->fc2t; d.fc2b = r->fc2b; d.bnf2s = r->bnf2s; d.bnf2b = r->bnf2b; d.fc3 = r->fc3; d.fc3b = r->fc3b;
-    d.fc1p = r->fc1p; d.fc2p = r->fc2p;
-    if (r->mode == P2P_REGRESS_FP16X2W) { d.wh1 = r->wh1_w; d.bn1s_h = r->bn1s_w; }      // conv1's stream of this mode's allocation
-    return d;
-}
-
-// counts: per item, the number of slots in the concatenated arrays (host memory); dev_counts (optional, device
-// memory, indexed like counts): how many of those slots hold a proposal -- the remaining work-groups exit at once.
-static int regress_batch_impl(const p2p_regressor *reg1, const p2p_regressor *reg2, int nitems,
-                              const p2p_pyramid *im1, const p2p_pyramid *im2, const int *counts, const int *dev_counts,
-                              const void *proposals, int is_float,
-                              float *matches1, float *probs1, float *raw1,
-                              float *matches2, float *probs2, float *raw2, void *workspace, size_t workspace_bytes,
-                              p2p_stream_t stream) {
-    P2P_REQUIRE(reg1 && im1 && im2 && counts, P2P_EINVAL, "p2p_regress: null argument");
-    P2P_REQUIRE(nitems >= 0, P2P_EINVAL, "p2p_regress: negative item count");
-    long long total = 0;
-    for (int i = 0; i < nitems; ++i) {
-        P2P_REQUIRE(counts[i] >= 0, P2P_EINVAL, "p2p_regress: negative proposal count");
-        total += counts[i];
-    }
-    if (total == 0) return P2P_OK;
-    P2P_REQUIRE(total < (1ll << 31), P2P_EINVAL, "p2p_regress: too many proposals");
-    P2P_REQUIRE(proposals, P2P_EINVAL, "p2p_regress: null proposals");
-    P2P_REQUIRE(reg2 ? (matches2 && probs2) : (matches1 && probs1), P2P_EINVAL, "p2p_regress: missing output buffers");
-    P2P_REQUIRE(!reg2 || reg2->mode == reg1->mode, P2P_EINVAL, "p2p_regress: the two regressors use different arithmetic modes");
-    for (int i = 0; i < nitems; ++i) {
-        const p2p_pyramid *im[2] = {im1 + i, im2 + i};
-        for (int s = 0; s < 2; ++s) {
-            P2P_REQUIRE(im[s]->height >= 8 && im[s]->width >= 8 && im[s]->height < 32768 && im[s]->width < 32768,
-                        P2P_EINVAL, "p2p_regress: item %d image %d size %dx%d must be within [8, 32767]", i, s + 1,
-                        im[s]->height, im[s]->width);
-            for (int j = 0; j < 4; ++j) P2P_REQUIRE(im[s]->level[j], P2P_EINVAL, "p2p_regress: null pyramid level");
-        }
-    }
-    const bool batched_fc = reg1->mode == P2P_REGRESS_FP16X2 || reg1->mode == P2P_REGRESS_FP16X2W;
-    if (batched_fc) {
-        int most = 0;
-        for (int i0 = 0; i0 < nitems; i0 += MAXB) {
-            int n = 0;
-            for (int b = i0; b < nitems && b < i0 + MAXB; ++b) n += counts[b];
-            most = std::max(most, n);
-        }
-        // the direct mode only parks the pooled features and the next level's proposals; the Winograd mode also the
-        // transformed conv2 input of a chunk (p2p_regress_workspace_bytes_mode)
-        const size_t need = (reg1->mode == P2P_REGRESS_FP16X2W ? regress_ws_floats((size_t)most) : regress_ws_base_floats((size_t)most)) * sizeof(float);
-        P2P_REQUIRE(workspace && ((uintptr_t)workspace & 127) == 0, P2P_EINVAL,
-                    "p2p_regress: a 128-byte aligned workspace of %zu bytes (p2p_regress_workspace_bytes_mode) is needed", need);
-        // too small: P2P_ENOMEM like every other workspace check of the library (a caller may grow the buffer and retry)
-        P2P_REQUIRE(workspace_bytes >= need, P2P_ENOMEM,
-                    "p2p_regress: workspace of %zu bytes (p2p_regress_workspace_bytes_mode) needed, got %zu", need, workspace_bytes);
-    }
+// one work-group per proposal slot
+int launch_regress_f32(const RegressArgs &a, int n, hipStream_t stream) {
     int dev = 0;
     P2P_HIP_CHECK(hipGetDevice(&dev));
     static DeviceOnce attr_set;
@@ -583,91 +357,8 @@ static int regress_batch_impl(const p2p_regressor *reg1, const p2p_regressor *re
                                           (int)LDS_BYTES));
         attr_set.set(dev);
     }
-    // launches of at most MAXB items; outputs/proposals are indexed by the global proposal number
-    int first_prop = 0;
-    for (int i0 = 0; i0 < nitems; i0 += MAXB) {
-        const int nb = (nitems - i0 < MAXB) ? nitems - i0 : MAXB;
-        RegressArgs a;
-        int n = 0;
-        for (int b = 0; b < nb; ++b) {
-            const p2p_pyramid *im[2] = {im1 + i0 + b, im2 + i0 + b};
-            for (int s = 0; s < 2; ++s) {
-                for (int j = 0; j < 4; ++j) a.item[b].pyr[s][j] = im[s]->level[j];
-                a.item[b].H[s] = im[s]->height;
-                a.item[b].W[s] = im[s]->width;
-            }
-            a.start[b] = n;
-            n += counts[i0 + b];
-        }
-        for (int b = nb; b <= MAXB; ++b) a.start[b] = n;
-        for (int b = nb; b < MAXB; ++b) a.item[b] = a.item[0];
-        a.nitems = nb;
-        a.dev_counts = dev_counts ? dev_counts + i0 : nullptr;
-        a.is_float = is_float; a.n = n; a.nlevels = reg2 ? 2 : 1;
-        a.proposals = is_float ? (const void *)((const float *)proposals + (size_t)first_prop * 4)
-                               : (const void *)((const long long *)proposals + (size_t)first_prop * 4);
-        a.reg[0] = to_dev(reg1);
-        a.reg[1] = reg2 ? to_dev(reg2) : a.reg[0];
-        auto adv = [&](float *p, int cols) { return p ? p + (size_t)first_prop * cols : nullptr; };
-        a.matches[0] = adv(matches1, 4); a.probs[0] = adv(probs1, 1); a.raw[0] = adv(raw1, 5);
-        a.matches[1] = adv(matches2, 4); a.probs[1] = adv(probs2, 1); a.raw[1] = adv(raw2, 5);
-        a.ws = (float *)workspace;      // launches of one call are ordered on the stream: they may share the scratch
-        if (n > 0) {
-            int st;
-            a.wU = nullptr; a.hinv = nullptr; a.lvl0 = 0; a.p0 = 0; a.p1 = n; a.mblocks = 0;
-            if (reg1->mode == P2P_REGRESS_FP16X2W) {
-                st = launch_regress_wino(a, n, (hipStream_t)stream);
-            } else if (reg1->mode == P2P_REGRESS_FP16X2) {
-                st = launch_regress_h2(a, n, (hipStream_t)stream);
-            } else {
-                hipLaunchKernelGGL(regress_kernel, dim3(n), dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
-                st = check_launch("regress_kernel");
-            }
-            if (st != P2P_OK) return st;
-        }
-        first_prop += n;
-    }
-    return P2P_OK;
+    hipLaunchKernelGGL(regress_kernel, dim3(n), dim3(NT), LDS_BYTES, stream, a);
+    return check_launch("regress_kernel");
 }
 
-extern "C" int p2p_regress_batch(const p2p_regressor *reg1, const p2p_regressor *reg2, int nitems,
-                                 const p2p_pyramid *im1, const p2p_pyramid *im2, const int *counts,
-                                 const void *proposals, int is_float,
-                                 float *matches1, float *probs1, float *raw1,
-                                 float *matches2, float *probs2, float *raw2, void *workspace, size_t workspace_bytes,
-                                 p2p_stream_t stream) {
-    return regress_batch_impl(reg1, reg2, nitems, im1, im2, counts, nullptr, proposals, is_float, matches1, probs1, raw1,
-                              matches2, probs2, raw2, workspace, workspace_bytes, stream);
-}
-
-extern "C" size_t p2p_regress_workspace_bytes(int n) {
-    return n > 0 ? regress_ws_floats((size_t)n) * sizeof(float) : 0;
-}
-
-extern "C" size_t p2p_regress_workspace_bytes_mode(int n, int mode) {
-    if (n <= 0 || mode == P2P_REGRESS_F32) return 0;
-    return (mode == P2P_REGRESS_FP16X2W ? regress_ws_floats((size_t)n) : regress_ws_base_floats((size_t)n)) * sizeof(float);
-}
-
-extern "C" int p2p_regress_batch_dev(const p2p_regressor *reg1, const p2p_regressor *reg2, int nitems,
-                                     const p2p_pyramid *im1, const p2p_pyramid *im2, const int *dev_counts, int stride,
-                                     const void *proposals, int is_float,
-                                     float *matches1, float *probs1, float *raw1,
-                                     float *matches2, float *probs2, float *raw2, void *workspace, size_t workspace_bytes,
-                                     p2p_stream_t stream) {
-    P2P_REQUIRE(dev_counts && stride >= 1 && nitems >= 0 && nitems <= 4096, P2P_EINVAL, "p2p_regress_batch_dev: bad argument");
-    std::vector<int> cap(nitems, stride);
-    return regress_batch_impl(reg1, reg2, nitems, im1, im2, cap.data(), dev_counts, proposals, is_float, matches1, probs1,
-                              raw1, matches2, probs2, raw2, workspace, workspace_bytes, stream);
-}
-
-extern "C" int p2p_regress(const p2p_regressor *reg1, const p2p_regressor *reg2,
-                           const p2p_pyramid *im1, const p2p_pyramid *im2,
-                           const void *proposals, int is_float, int n,
-                           float *matches1, float *probs1, float *raw1,
-                           float *matches2, float *probs2, float *raw2, void *workspace, size_t workspace_bytes,
-                           p2p_stream_t stream) {
-    P2P_REQUIRE(n >= 0, P2P_EINVAL, "p2p_regress: negative proposal count");
-    return p2p_regress_batch(reg1, reg2, 1, im1, im2, &n, proposals, is_float, matches1, probs1, raw1, matches2, probs2,
-                             raw2, workspace, workspace_bytes, stream);
-}
+}  // namespace p2p

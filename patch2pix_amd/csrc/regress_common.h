@@ -1,8 +1,11 @@
-// Pieces shared by the fine-stage kernels (exact-f32 MFMA, regress.hip; fp16x2, regress_h2.hip / regress_wino.hip).
+// Pieces shared by the fine-stage sources: the kernels (exact-f32 MFMA, regress.hip; fp16x2, regress_h2.hip / regress_wino.hip),
+// each with its weight packer and its launcher, and the host API over them (regress_api.hip: the handle, the modes, the C ABI).
 #pragma once
 #include "p2p_common.h"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <vector>
 
 namespace p2p {
 
@@ -41,6 +44,9 @@ struct RegressArgs {
     float *hinv;
     int lvl0, p0, p1, mblocks;
 };
+// kernel arguments: a field added, moved or retyped moves the kernarg offsets of every fine-stage kernel, and with them its code
+// (tools/isa_diff.py then reports the kernels as changed, which a host-side change must not)
+static_assert(sizeof(RegDev) == 24 * sizeof(void *) && sizeof(RegressArgs) == 1864, "kernel-argument layout of the fine stage");
 
 // scratch of the kernels whose FC tail is batched over a work-group's proposals (regress_h2.hip): the pooled
 // convolution features V [level][n][512] and the un-truncated mid matches [n][4] the fine level starts from
@@ -341,6 +347,51 @@ static inline void pack_fc_mfma(const float *w, int N, float *out) {
                     out[(((size_t)S * (N / 16) + t) * 64 + lane) * 4 + j] = w[(size_t)(16 * t + (lane & 15)) * 512 + 16 * S + 4 * (lane >> 4) + j];
 }
 
+// ---- host side: what the weight packers share --------------------------------------------------------------------
+// fp32 -> two fp16 planes: v = hi + lo to within 2^-24 |v| (both round to nearest even, like the kernels' own splits)
+static inline void split_fp16_planes(float v, uint16_t *hi, uint16_t *lo) {
+    const _Float16 h = (_Float16)v;
+    *hi = __builtin_bit_cast(uint16_t, h);
+    *lo = __builtin_bit_cast(uint16_t, (_Float16)(v - (float)h));
+}
+// the exponent t for which 2^t brings a channel's largest weight magnitude mx into [2^11, 2^12) (exact scaling; undone in the
+// folded BatchNorm scale, fold_exponent); 0 for a channel of zeros or with a non-finite weight
+static inline int plane_exponent(double mx) {
+    if (!(mx > 0.0) || !std::isfinite(mx)) return 0;
+    int e;
+    std::frexp(mx, &e);          // mx = m * 2^e, m in [0.5, 1)
+    return 12 - e;
+}
+// out[n] = bn_scale[n] * 2^-(bias + t[n]): a convolution whose weights carried 2^t[n] (and whose activations 2^bias)
+// accumulates 2^(bias + t[n]) x the true sum
+static inline void fold_exponent(const float *bn_scale, const int *t, int bias, float *out) {
+    for (int n = 0; n < 512; ++n) out[n] = std::ldexp(bn_scale[n], -bias - t[n]);
+}
+// compute units of a device (>= 1; the grids of the persistent kernels), asked once per device and process; P2P_EHIP (< 0) if the
+// runtime refuses
+static inline int device_cu_count(int dev) {
+    static std::atomic<int> cus[64];
+    const bool slot = dev >= 0 && dev < 64;
+    int ncu = slot ? cus[dev].load(std::memory_order_relaxed) : 0;
+    if (ncu > 0) return ncu;
+    P2P_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    ncu = std::max(ncu, 1);
+    if (slot) cus[dev].store(ncu, std::memory_order_relaxed);
+    return ncu;
+}
+
+// ---- per source: stream sizes, packer (host), launcher ------------------------------------------------------------
+// regress.hip: the K axis in chunks of 8, stream order [wave 8][chunk][n-tile 2][lane 64][4]
+constexpr int K1_CHUNKS_PER_TAP = 65;   // 1 (level-0 of both images, 6 ch padded to 8) + 2*(8+8+16)
+constexpr int K1_CHUNKS = 9 * K1_CHUNKS_PER_TAP;
+constexpr int K2_CHUNKS_PER_TAP = 64;   // 512 channels / 8
+constexpr int K2_CHUNKS = 9 * K2_CHUNKS_PER_TAP;
+constexpr int PF = 2;                   // weight prefetch distance (chunks); buffers are padded by PF chunks
+constexpr size_t WP1_FLOATS = (size_t)8 * (K1_CHUNKS + PF) * 2 * 64 * 4;
+constexpr size_t WP2_FLOATS = (size_t)8 * (K2_CHUNKS + PF) * 2 * 64 * 4;
+void pack_f32_weights(const float *conv1_w, const float *conv2_w, float *wp1, float *wp2);
+int launch_regress_f32(const RegressArgs &a, int n, hipStream_t stream);
+
 // regress_h2.hip: the K axis of the two convolutions in slabs of 16
 constexpr int S1_SLABS = 4 + 9 * 2 * 16; // conv1: 4 slabs of level 0 (3 ch x 9 taps x 2 images, padded 54 -> 64), then per
                                         // (tap, image) 4 + 4 + 8 slabs of 16 channels of levels 1, 2, 3
@@ -360,6 +411,19 @@ int launch_regress_h2_conv1(const RegressArgs &a, int n, hipStream_t stream);   
 // regress_wino.hip: conv2 as Winograd F(2x2, 3x3) GEMMs; filter blocks [position 16][column block 4][K chunk 16][WINO_BLK]
 constexpr size_t WW2_FLOATS = (size_t)16 * 4 * 16 * (WINO_BLK / 4);
 void pack_wino_weights(const float *conv2_w, float *ww2, int *t2);                // host
-int launch_regress_wino(RegressArgs a, int n, hipStream_t stream);
+int launch_regress_wino(const RegressArgs &a, int n, hipStream_t stream);
 
 }  // namespace p2p
+
+// The opaque handle of include/p2p_hip.h.  A mode's kernels see the regressor through ONE RegDev: `common` (the BatchNorm / FC
+// pointers into `dev`, every stream pointer null) plus the stream pointers of that mode's own allocation.
+constexpr int P2P_REGRESS_NMODES = 3;
+struct p2p_regressor {
+    int device;        // the device the handle was created on: every later allocation (another mode's weight stream) goes there
+    int mode;          // P2P_REGRESS_F32 | P2P_REGRESS_FP16X2 | P2P_REGRESS_FP16X2W
+    float *dev;        // BatchNorm folds + FC layers (every mode)
+    float *stream[P2P_REGRESS_NMODES];      // a mode's convolution weights in its kernels' stream order (+ the BatchNorm scales with
+                                            // its exponents folded in); packed on the mode's first selection, null until then
+    std::vector<float> conv1_w, conv2_w, bn1s_host, bn2s_host;   // host copies the packings are built from
+    p2p::RegDev common, view[P2P_REGRESS_NMODES];
+};

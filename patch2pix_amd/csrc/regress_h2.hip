@@ -94,9 +94,6 @@ constexpr int XUB = XNPL * 1024;
 //            rows 0-3/12-15 of K quarter q take the even and rows 4-11 of quarter q + 1 the odd slots;
 //   the dead rows of a cell tile (and, in conv2, taps outside the 8 x 8 map) read zeros from the piece of a zero area that
 //   keeps them on the slot of their virtual row -- one shared zero cell collided with a live row in half of the groups.
-// level 1 (round 6): two fp16 planes like levels 2 / 3 -- [plane][9 grid rows][9 cells][64 ch (+16 B)]; a cell is 9 slots, a grid
-// row 88 slots = 8 (mod 16): the 16 lanes of a ds_read_b128 service group (4 y x 4 x of the tap's pixels) land on 16 different slots
-// ({0,9,2,11} + {0,8,..} ...: see "Bank slots"), as the fp32 grid of rounds 4-5 did with its 17-slot cells
 constexpr int XST1 = 64 * 2 + 16;                                 // bytes per level-1 cell (9 slots)
 constexpr int XRP1 = 9 * XST1 + 112;                              // level-1 grid row: 88 slots = 8 (mod 16)
 constexpr int XPL1 = 9 * XRP1;                                    // plane stride
@@ -158,7 +155,7 @@ __device__ __forceinline__ unsigned short f2e(float f) { return __builtin_bit_ca
 __device__ __forceinline__ float e2f(unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); }
 __device__ __forceinline__ float pk_lo(unsigned h) { return (float)__builtin_bit_cast(xe2, h)[0]; }
 __device__ __forceinline__ float pk_hi(unsigned h) { return (float)__builtin_bit_cast(xe2, h)[1]; }
-// v = p0 + p1 (+ p2): the planes of one value, stored XPLST bytes apart
+// v = p0 + p1: the planes of one value, stored plane_stride bytes apart
 __device__ __forceinline__ void store_planes(unsigned char *dst, int plane_stride, float v) {
     const unsigned short p0 = f2e(v);
     const float r1 = v - e2f(p0);
@@ -189,7 +186,6 @@ __device__ __forceinline__ void splitn(const f32x4 &xa, const f32x4 &xb, float s
 #ifdef P2P_X3_TIMING                    // phase lengths in s_memtime ticks -> args.raw[0] (tools/x3_timing.py)
 // per-wave counters in LDS (14 more live SGPRs spill): [wave][16] unsigned behind the misc block
 #define XTL_() ((unsigned *)(smb + XSM_MISC + 64) + wave * 16)
-#define XT_DECL
 #define XT_START { const unsigned n_ = (unsigned)__builtin_amdgcn_s_memtime(); if (P2P_LANE_ID() < 16) XTL_()[P2P_LANE_ID()] = (P2P_LANE_ID() == 15) ? n_ : 0u; }
 #define XT(i) { const unsigned n_ = (unsigned)__builtin_amdgcn_s_memtime(); if (P2P_LANE_ID() == 0) { unsigned *x_ = XTL_(); x_[i] += n_ - x_[15]; x_[15] = n_; } }
 #if P2P_X3_TIMING >= 2                  // also the three ranges inside a conv1 step (stamps inside the hot loop: spills)
@@ -198,7 +194,6 @@ __device__ __forceinline__ void splitn(const f32x4 &xa, const f32x4 &xb, float s
 #define XTL(i)
 #endif
 #else
-#define XT_DECL
 #define XT_START
 #define XT(i)
 #define XTL(i)
@@ -209,7 +204,7 @@ __device__ __forceinline__ void splitn(const f32x4 &xa, const f32x4 &xb, float s
 #define XLOADR(R, P) R[0] = *(const f32x4 *)(P); R[1] = *(const f32x4 *)((P) + 16);
 // pre-split A fragment of one m-tile: one 16-byte LDS read per plane, PL = plane stride
 #define XLOADP(S, P, PL) { _Pragma("unroll") for (int q_ = 0; q_ < XNPL; ++q_) S[q_] = *(const f32x4 *)((P) + q_ * (PL)); }
-// weights of the unit `AHEAD` units after the current stream position: 3 planes
+// weights of the unit `AHEAD` units after the current stream position: XNPL planes
 // (wb = wave-uniform stream position, kept in SGPRs; wlane = 16 * lane: one VGPR addresses every weight load)
 #define XLOADB(BUF, AHEAD)                                                               \
     { unsigned wo_ = (AHEAD) * XUB; P2P_OPAQUE_S(wo_);        /* opaque: keeps "+ AHEAD units" on the scalar side */  \
@@ -496,7 +491,7 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
         // lane coordinates derived from the opaque copy: nothing lane-dependent is loop-invariant for the compiler, so
         // nothing is hoisted out of the level loop and kept (or spilled) across its high-pressure phases
         const int half = (tidv >> 5) & 1, l31 = tidv & 31;
-        XT_DECL XT_START
+        XT_START
         // waves 4-7 are the younger wave of their SIMD and lose the issue arbitration on every MFMA segment (they were
         // ~20 % slower between barriers): static priority for that half, no per-segment flips
         if (wave >= 4) __builtin_amdgcn_s_setprio(1);
@@ -566,7 +561,7 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
                             if (j == 1) {
                                 *(float *)(smb + XSHARED + XTMP1 + img * XTMP1IMG + rem * XTMP1ST + c * 4) = v;
                             } else {
-                                // fp32 copy for the scale pass + the planes (exact: v = p0 + p1 + p2)
+                                // fp32 copy for the scale pass + the planes (exact: v = p0 + p1)
                                 *(float *)(smb + XSHARED + img * XTMPIMG + ((j == 2) ? rem * XTMP2ST : XTMP3 + rem * XTMP3ST) + c * 4) = v;
                             }
                         }
@@ -989,24 +984,22 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
             }
             XT(9)
         } else {
-        // BN1 -> H.  Two planes: every wave writes the planes of its 64 channels into its chunk (wave >> 1).  Three planes:
-        // chunk 0 (channels of waves 0, 1) as planes, the other chunks wait as fp32
+        // BN1 -> H: every wave writes the two planes of its 64 channels into its chunk (wave >> 1)
         {
             if (tidv < 4 * XNPL * (2 * HST / 16)) {  // the two all-zero padding rows of every plane (of every chunk)
                 const int ch = tidv / (XNPL * (2 * HST / 16)), pq = tidv - ch * (XNPL * (2 * HST / 16));
                 const int pl = pq / (2 * HST / 16), q = pq - pl * (2 * HST / 16);
                 float zf = 0.f;
                 P2P_OPAQUE(zf);
-                if (HCHUNK != 0 || ch == 0) *(f32x4 *)(smb + ch * HCHUNK + pl * HPL + 64 * HST + q * 16) = (f32x4){zf, zf, zf, zf};
+                *(f32x4 *)(smb + ch * HCHUNK + pl * HPL + 64 * HST + q * 16) = (f32x4){zf, zf, zf, zf};
             }
             const int chunk = wave >> 1;
-            const int hv = half, lv = l31;
             // H is scaled by the power of two that brings its largest magnitude to [2^12, 2^13) before it is split
             {
                 float mx = 0.f;
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
-                    const int n = wave * 64 + u * 32 + lv;
+                    const int n = wave * 64 + u * 32 + l31;
                     const float s = R_.bn1s_h[n], b = R_.bn1b[n];
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
@@ -1021,13 +1014,13 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
             const float hmul = __int_as_float((266 - clampi((((const int *)misc)[14] >> 23) & 0xff, 20, 250)) << 23);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                const int n = wave * 64 + u * 32 + lv;
-                const int cc = (wave & 1) * 64 + u * 32 + lv;                // channel inside the chunk
+                const int n = wave * 64 + u * 32 + l31;
+                const int cc = (wave & 1) * 64 + u * 32 + l31;                // channel inside the chunk
                 const float s = R_.bn1s_h[n], b = R_.bn1b[n];
                 // channels (cc, cc + 1) sit in adjacent lanes: the even lane stores the pair's first plane, the odd lane its
                 // second plane -- one 4-byte store per value instead of two 2-byte ones
-                const bool odd = lv & 1;
-                unsigned char *dplane = smb + chunk * HCHUNK + (odd ? HPL : 0) + 4 * hv * HST + (cc & ~1) * 2;
+                const bool odd = l31 & 1;
+                unsigned char *dplane = smb + chunk * HCHUNK + (odd ? HPL : 0) + 4 * half * HST + (cc & ~1) * 2;
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     const f32x16 &a = (t == 0) ? (u == 0 ? acc00 : acc01) : (u == 0 ? acc10 : acc11);
@@ -1172,32 +1165,18 @@ static void split_conv1_index(int slab, int half, int j, int &ch, int &tap) {
     ch = img * 259 + base + 8 * half + j;
 }
 
-static uint16_t host_e(float v) {
-    return __builtin_bit_cast(uint16_t, (_Float16)v);
-}
-static float host_e2f(uint16_t e) {
-    return (float)__builtin_bit_cast(_Float16, e);
-}
+// element j of lane `lane` in both planes of the unit that starts at unit_base
 static void putn(uint16_t *d, size_t unit_base, int lane, int j, float v) {
-    const uint16_t p0 = host_e(v);
-    const float r1 = v - host_e2f(p0);
-    const uint16_t p1 = host_e(r1);
-    d[(unit_base + lane) * 8 + j] = p0;
-    d[(unit_base + 64 + lane) * 8 + j] = p1;
+    split_fp16_planes(v, &d[(unit_base + lane) * 8 + j], &d[(unit_base + 64 + lane) * 8 + j]);
 }
 
 // fp16 planes: every output channel's weights are scaled by the power of two 2^t[n] that brings the largest of them into
 // [2^11, 2^12) (exact; undone in the folded BatchNorm scale).
 static void channel_exponents(const float *w, int rows, int per_row, int *t) {
     for (int n = 0; n < rows; ++n) {
-        t[n] = 0;
         float mx = 0.f;
         for (int k = 0; k < per_row; ++k) mx = std::max(mx, std::fabs(w[(size_t)n * per_row + k]));
-        if (mx > 0.f && std::isfinite(mx)) {
-            int e;
-            std::frexp(mx, &e);          // mx = m * 2^e, m in [0.5, 1)
-            t[n] = 12 - e;
-        }
+        t[n] = plane_exponent(mx);
     }
 }
 
@@ -1275,16 +1254,15 @@ static int launch_h2(const RegressArgs &a, int n, bool wino, hipStream_t stream)
     int dev = 0;
     P2P_HIP_CHECK(hipGetDevice(&dev));
     static DeviceOnce attr_set;
-    static std::atomic<int> cus[64];
-    int ncu_dev = (dev >= 0 && dev < 64 && attr_set.done(dev)) ? cus[dev].load(std::memory_order_relaxed) : 0;
-    if (ncu_dev <= 0) {
+    if (!attr_set.done(dev)) {
         P2P_HIP_CHECK(hipFuncSetAttribute((const void *)regress_h2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)XSM_BYTES));
         P2P_HIP_CHECK(hipFuncSetAttribute((const void *)regress_h2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)XSM_BYTES));
-        P2P_HIP_CHECK(hipDeviceGetAttribute(&ncu_dev, hipDeviceAttributeMultiprocessorCount, dev));
-        if (dev >= 0 && dev < 64) { cus[dev].store(ncu_dev, std::memory_order_relaxed); attr_set.set(dev); }
+        attr_set.set(dev);
     }
+    const int ncu_dev = device_cu_count(dev);
+    if (ncu_dev < 0) return ncu_dev;
     // persistent work-groups: one fits a compute unit (LDS), each walks its share of the proposals
 #ifdef XF_GRID_CAP                       // power experiment: only this many work-groups (= busy compute units)
     const int ncu = std::min(ncu_dev, XF_GRID_CAP);
@@ -1292,8 +1270,8 @@ static int launch_h2(const RegressArgs &a, int n, bool wino, hipStream_t stream)
     const int ncu = ncu_dev;
 #endif
     P2P_REQUIRE(a.ws, P2P_EINVAL, "%s: the scratch buffer is missing", "regress_h2_kernel");
-    if (wino) hipLaunchKernelGGL(regress_h2_kernel<true>, dim3(std::min(n, std::max(ncu, 1))), dim3(NT), XSM_BYTES, stream, a);
-    else hipLaunchKernelGGL(regress_h2_kernel<false>, dim3(std::min(n, std::max(ncu, 1))), dim3(NT), XSM_BYTES, stream, a);
+    if (wino) hipLaunchKernelGGL(regress_h2_kernel<true>, dim3(std::min(n, ncu)), dim3(NT), XSM_BYTES, stream, a);
+    else hipLaunchKernelGGL(regress_h2_kernel<false>, dim3(std::min(n, ncu)), dim3(NT), XSM_BYTES, stream, a);
     return check_launch("regress_h2_kernel");
 }
 

@@ -224,9 +224,6 @@ __global__ __launch_bounds__(NT, 2) void regress_fc_kernel(RegressArgs args, int
 // --------------------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------------------
-static uint16_t w_e(float v) { return __builtin_bit_cast(uint16_t, (_Float16)v); }
-static float w_e2f(uint16_t e) { return (float)__builtin_bit_cast(_Float16, e); }
-
 // transformed filters of conv2 as the B blocks of wino_gemm_kernel; t2[n] = the exponent output channel n was scaled by
 void pack_wino_weights(const float *conv2_w, float *out, int *t2) {
     static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
@@ -245,14 +242,7 @@ void pack_wino_weights(const float *conv2_w, float *out, int *t2) {
                     mx[n] = std::max(mx[n], std::fabs(v));
                 }
         }
-    for (int n = 0; n < 512; ++n) {
-        t2[n] = 0;
-        if (mx[n] > 0.0 && std::isfinite(mx[n])) {
-            int e;
-            std::frexp(mx[n], &e);
-            t2[n] = 12 - e;
-        }
-    }
+    for (int n = 0; n < 512; ++n) t2[n] = plane_exponent(mx[n]);
     uint16_t *d = (uint16_t *)out;
     for (int p = 0; p < 16; ++p)
         for (int n = 0; n < 512; ++n) {
@@ -260,11 +250,9 @@ void pack_wino_weights(const float *conv2_w, float *out, int *t2) {
             for (int k = 0; k < 512; ++k) {
                 const int kc = k >> 5, qq = (k >> 3) & 3, e = k & 7;
                 const float v = (float)std::ldexp(wt[((size_t)p * 512 + n) * 512 + k], t2[n]);
-                const uint16_t h0 = w_e(v), h1 = w_e(v - w_e2f(h0));
                 const size_t blk = ((size_t)(p * 4 + nb) * 16 + kc) * (WINO_BLK / 2);       // in fp16 elements
                 const size_t in = (size_t)(col * 4 + (qq ^ ((col >> 2) & 3))) * 8 + e;
-                d[blk + in] = h0;
-                d[blk + 128 * 32 + in] = h1;
+                split_fp16_planes(v, &d[blk + in], &d[blk + 128 * 32 + in]);
             }
         }
 }
@@ -272,7 +260,8 @@ void pack_wino_weights(const float *conv2_w, float *out, int *t2) {
 // Both levels of a launch: per level, chunks of whole units of 256 proposals (wino_nchunks / wino_chunk_range, at most WINO_CHUNK
 // each) run conv1 -> U (regress_h2_kernel<true>) and the
 // GEMMs (U -> V); then the level's FC tail, whose matches are the next level's proposals.
-int launch_regress_wino(RegressArgs a, int n, hipStream_t stream) {
+int launch_regress_wino(const RegressArgs &args, int n, hipStream_t stream) {
+    RegressArgs a = args;      // the level and the chunk of a launch are filled in below
     int dev = 0;
     P2P_HIP_CHECK(hipGetDevice(&dev));
     static DeviceOnce attr_set;
@@ -281,9 +270,8 @@ int launch_regress_wino(RegressArgs a, int n, hipStream_t stream) {
         P2P_HIP_CHECK(hipFuncSetAttribute((const void *)regress_fc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FC_LDS_BYTES));
         attr_set.set(dev);
     }
-    int ncu = 0;
-    P2P_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    ncu = std::max(ncu, 1);
+    const int ncu = device_cu_count(dev);
+    if (ncu < 0) return ncu;
     P2P_REQUIRE(a.ws, P2P_EINVAL, "%s: the scratch buffer is missing", "launch_regress_wino");
     unsigned char *wsU = (unsigned char *)(a.ws + wino_u_offset_floats((size_t)n));
     float *hinv = a.ws + wino_hinv_offset_floats((size_t)n);

@@ -104,9 +104,10 @@ def regress_scratch(emu, n):
     return ws, ctypes.c_void_p((ws.data_ptr() + 127) & ~127), need
 
 
-def regress(emu, reg1, reg2, pyr1, pyr2, proposals):
+def regress(emu, reg1, reg2, pyr1, pyr2, proposals, expect_status=0):
     """One pair through p2p_regress_batch: pyr*: the 4 maps of feat_idx [0,1,2,3] (CPU fp32), proposals [n,4]
-    int64 or float32.  Returns dict matches1/probs1/raw1 (+ *2 with reg2)."""
+    int64 or float32.  Returns dict matches1/probs1/raw1 (+ *2 with reg2).  expect_status: the error code the call must
+    return instead of P2P_OK (the outputs are then meaningless)."""
     def pyramid(levels):
         lv = [t.contiguous() for t in levels]
         q = real.Pyramid()
@@ -124,12 +125,16 @@ def regress(emu, reg1, reg2, pyr1, pyr2, proposals):
     arr_a, arr_b = (real.Pyramid * 1)(pa), (real.Pyramid * 1)(pb)
     cnt = (ctypes.c_int * 1)(n)
     ws, wsp, wsn = regress_scratch(emu, n)
-    check(emu, emu.p2p_regress_batch(reg1, reg2 if two else None, 1, arr_a, arr_b, cnt, proposals.data_ptr(),
-                                     int(proposals.is_floating_point()), out["matches1"].data_ptr(),
-                                     out["probs1"].data_ptr(), out["raw1"].data_ptr(),
-                                     out["matches2"].data_ptr() if two else None, out["probs2"].data_ptr() if two else None,
-                                     out["raw2"].data_ptr() if two else None, wsp, wsn, None), "p2p_regress_batch")
+    st = emu.p2p_regress_batch(reg1, reg2 if two else None, 1, arr_a, arr_b, cnt, proposals.data_ptr(),
+                               int(proposals.is_floating_point()), out["matches1"].data_ptr(),
+                               out["probs1"].data_ptr(), out["raw1"].data_ptr(),
+                               out["matches2"].data_ptr() if two else None, out["probs2"].data_ptr() if two else None,
+                               out["raw2"].data_ptr() if two else None, wsp, wsn, None)
     del ka, kb
+    if expect_status:
+        assert st == expect_status, f"p2p_regress_batch returned {st}, expected {expect_status}"
+    else:
+        check(emu, st, "p2p_regress_batch")
     return out
 
 

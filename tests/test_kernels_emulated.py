@@ -107,6 +107,103 @@ def test_regressors_against_reference_golden(mode, emu, sd):
         assert (out["probs1"] - torch.from_numpy(g[tag + "_probs"][:n])).abs().max() <= SCORE_TOL
 
 
+def _seeded_conv_weights():
+    """conv1 / conv2 weights of a regressor with per-channel magnitudes over 13 octaves and one channel of zeros each."""
+    rng = np.random.default_rng(20261016)
+    out = []
+    for cin in (518, 512):
+        w = rng.standard_normal((512, cin, 3, 3)).astype(np.float32)
+        w *= np.exp2(rng.integers(-9, 4, (512, 1, 1, 1))).astype(np.float32)
+        out.append(w)
+    out[0][7] = 0.0
+    out[1][300] = 0.0
+    return out
+
+
+# sha256 of what the packers wrote for _seeded_conv_weights().  Recorded from the build of commit 97c98c9 -- the parent of the
+# change that split regress_api.hip from regress.hip and moved the fp16 split, the channel exponent and the f32 packing loops
+# into shared functions -- NOT from the code under test: pack_h2_weights / pack_wino_weights called in that build, the f32
+# streams read back from a handle of that build in mode f32 (it had no pack_f32_weights).
+PACKED_SHA256 = {
+    "wh1": "ce7ef5f0a6dfe9fcf8a04aead1e48b8c26709a79280f947012d116ab8771b755",
+    "wh2": "5849a938f765dbbc8ed1bc168d4b32c30aef4d1234383bc0f7fcbef86df09198",
+    "h2_t1": "fcee7e4b64524e27fe925954f14fa9dbe511aea43f8eacf2374e917705f92a56",
+    "h2_t2": "eec08cb2e825e39280ce255dbd082f73b6b9355857132291bfbbce0442724d02",
+    "ww2": "e24349ed0a77a0c3bf8d54f4e48300e2cfcb54c4c9fd126db06f6763777bc02b",
+    "wino_t2": "60845544294a4fd7c5b7b247239975eada41e0ce49f9660ad8120d113a2982b1",
+    "wp1": "17edffe4225aee4173a01797d41e522b865fb28c75a50afdc3a55b23507d00e5",
+    "wp2": "04c9129b305a90ec4be54a609d87c422c1299ef1b579e76e9966a2b629b12b3e",
+}
+
+
+def test_weight_packers_write_the_recorded_bytes(emu):
+    """The three host packers (regress_h2.hip, regress_wino.hip, regress.hip; C++ symbols of namespace p2p, declared in
+    regress_common.h) on seeded weights: every stream and every exponent table, bit for bit, against PACKED_SHA256.
+    The int tables start as 99: a channel the packer leaves alone would show."""
+    import ctypes
+    import hashlib
+    F, I = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)
+
+    def fn(mangled, argtypes):
+        f = getattr(emu, mangled)
+        f.restype, f.argtypes = None, argtypes
+        return f
+
+    pack_h2 = fn("_ZN3p2p15pack_h2_weightsEPKfS1_PfS2_PiS3_", [F, F, F, F, I, I])
+    pack_wino = fn("_ZN3p2p17pack_wino_weightsEPKfPfPi", [F, F, I])
+    pack_f32 = fn("_ZN3p2p16pack_f32_weightsEPKfS1_PfS2_", [F, F, F, F])
+    # WH1_FLOATS, WH2_FLOATS, WW2_FLOATS, WP1_FLOATS, WP2_FLOATS of regress_common.h
+    floats = {"wh1": 8 * (2 * 292 + 8) * 512, "wh2": 8 * (2 * 288 + 8) * 512, "ww2": 16 * 4 * 16 * 4096,
+              "wp1": 8 * (585 + 2) * 512, "wp2": 8 * (576 + 2) * 512}
+    got = {k: np.zeros(n, np.float32) for k, n in floats.items()}
+    got.update({k: np.full(512, 99, np.int32) for k in ("h2_t1", "h2_t2", "wino_t2")})
+    fp, ip = (lambda k: got[k].ctypes.data_as(F)), (lambda k: got[k].ctypes.data_as(I))
+    c1, c2 = _seeded_conv_weights()
+    w1, w2 = c1.ctypes.data_as(F), c2.ctypes.data_as(F)
+    pack_h2(w1, w2, fp("wh1"), fp("wh2"), ip("h2_t1"), ip("h2_t2"))
+    pack_wino(w2, fp("ww2"), ip("wino_t2"))
+    pack_f32(w1, w2, fp("wp1"), fp("wp2"))
+    assert got["h2_t1"][7] == 0 and got["h2_t2"][300] == 0 and got["wino_t2"][300] == 0       # the channels of zeros
+    for k, want in PACKED_SHA256.items():
+        assert hashlib.sha256(got[k].tobytes()).hexdigest() == want, f"{k}: the packed bytes changed"
+    # conv1's stream alone (what P2P_REGRESS_FP16X2W packs: conv2_w null) is the same stream
+    alone, t1 = np.zeros(floats["wh1"], np.float32), np.full(512, 99, np.int32)
+    pack_h2(w1, None, alone.ctypes.data_as(F), None, t1.ctypes.data_as(I), None)
+    assert hashlib.sha256(alone.tobytes()).hexdigest() == PACKED_SHA256["wh1"] and np.array_equal(t1, got["h2_t1"])
+
+
+def test_mode_switching_equals_fresh_handles(emu, sd):
+    """A mode's kernels see a regressor through that mode's own view of the handle (regress_api.hip).  A mid + fine pair
+    switched f32 -> fp16x2w -> fp16x2 -> fp16x2w gives, in every mode, what a pair created and set to that mode directly
+    gives, bit for bit -- also in the mode it comes back to, and in fp16x2w, whose conv1 stream and BatchNorm scale are
+    the fp16x2 fields of its own allocation.  A pair in two different modes is refused."""
+    from patch2pix_amd import _lib as real
+    sub = lambda p: {k[len(p):]: v for k, v in sd.items() if k.startswith(p)}
+    H, W = 48, 64
+    p1, p2 = synthetic.make_pyramid(7, H, W), synthetic.make_pyramid(8, H, W)
+    props = torch.tensor([[0, 0, W, H], [31, 17, 5, 40], [20, 30, 44, 9]])
+    fresh = {}
+    for mode in ("f32", "fp16x2w", "fp16x2"):
+        pair = [emu_lib.regressor_create(emu, sub(p), mode) for p in ("regress_mid.", "regress_fine.")]
+        fresh[mode] = emu_lib.regress(emu, pair[0], pair[1], p1[:4], p2[:4], props)
+        for h in pair:
+            emu.p2p_regressor_destroy(h)
+    mid, fine = [emu_lib.regressor_create(emu, sub(p), "fp16x2w") for p in ("regress_mid.", "regress_fine.")]
+    for mode in ("f32", "fp16x2w", "fp16x2", "fp16x2w"):
+        for h in (mid, fine):
+            emu_lib.check(emu, emu.p2p_regressor_set_mode(h, real.REGRESS_MODES[mode]), "p2p_regressor_set_mode")
+            assert emu.p2p_regressor_get_mode(h) == real.REGRESS_MODES[mode]
+        out = emu_lib.regress(emu, mid, fine, p1[:4], p2[:4], props)
+        for k, v in fresh[mode].items():
+            assert torch.equal(out[k], v), f"{k} after switching to {mode}: max |d| {float((out[k] - v).abs().max()):.3e}"
+    emu_lib.check(emu, emu.p2p_regressor_set_mode(mid, real.REGRESS_MODES["fp16x2"]), "p2p_regressor_set_mode")
+    emu_lib.regress(emu, mid, fine, p1[:4], p2[:4], props, expect_status=-1)      # P2P_EINVAL: fp16x2 + fp16x2w
+    assert b"different arithmetic modes" in emu.p2p_last_error()
+    assert emu.p2p_regressor_set_mode(mid, 1) == -1 and emu.p2p_regressor_get_mode(mid) == real.REGRESS_MODES["fp16x2"]
+    for h in (mid, fine):
+        emu.p2p_regressor_destroy(h)
+
+
 def test_persistent_regressor_walks_many_proposals(sd, tmp_path):
     """The fp16x2 kernel's work-groups are persistent: each walks its share of the proposals and then runs the FC tail of all
     of them as batches of 16 rows on the f32 matrix path.  ONE emulated compute unit (a fresh process: the count is read
