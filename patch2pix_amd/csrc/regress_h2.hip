@@ -21,9 +21,17 @@
 //     into the BatchNorm scale that follows);
 //   * H = BN1(conv1), the input of conv2: per proposal the power of two that brings max |H| to [2^12, 2^13) (a
 //     work-group reduction on the accumulators); BN2's scale is multiplied by its inverse.
-// Elements more than 2^17 below the largest of their tensor lose relative precision (their second plane becomes an fp16
-// subnormal, absolute error 2^-25 on the scaled value = 2^-37 of the largest), which is far below the rounding of the
-// fp32 accumulation.  A product is
+// Elements more than 2^17 below the largest of their tensor lose relative precision: their second plane becomes an fp16
+// subnormal, absolute error 2^-25 on the scaled value = 2^-37 of the largest, i.e. a relative error of 2^(k - 37) for an
+// element 2^k below it -- one bit per octave.  As an ABSOLUTE error that is far below the rounding of the fp32
+// accumulation, but two later steps re-normalise small elements and turn it back into a relative one: the per-pixel L2
+// scale of the fold blows a dim pixel of a patch that also holds a 2^k brighter one back up to unit norm, and a conv2
+// weight column can be large exactly where its H channel is small.  Measured (tests/test_regress_range_emulated.py,
+// tests/test_gpu_regress_range.py; table in DESIGN.md, "Numeric domain of the fp16x2 paths"): up to a contrast of 2^16
+// inside a patch, or between the channels of H, the results stay where they are for ordinary inputs (~1e-4 px, 1e-6 in
+// the score, against the bars 1e-3 / 1e-5); at 2^20 both errors reach the bars (5e-4 ... 1.5e-3 px, 1e-5 ... 3e-5), at
+// 2^24 they are past them (4e-3 ... 2.5e-2 px), at 2^28 the coordinates are off by 0.05 ... 0.5 px: a factor of ~2^4 per
+// four octaves, as the lost bits predict.  Mode f32 does not have this limit.  A product is
 //     a * b ~= a0*b0 + (a0*b1 + a1*b0)        (the dropped a1*b1 is <= 2^-24 |a*b|),   fp32 accumulation
 // = 3 v_mfma_f32_32x32x16_f16.  Measured against an fp64 evaluation it is as accurate as the exact-f32 MFMA kernel
 // (tools/margin_sweep.py); ceiling 2500 / 3 = 833 TFLOP/s of algorithmic fp32 work.

@@ -9,7 +9,11 @@
 //
 //   U_p[row][k] = (B^T d B)[i][j]   d = the 4 x 4 window (stride 2, zero ring) of H = BN1(conv1) around tile (ty, tx), channel k;
 //                                   row = 16 * proposal + 4 * ty + tx; written by regress_h2_kernel<true> (regress_h2.hip),
-//                                   scaled per proposal so that |U| < 2^13, as two fp16 planes
+//                                   scaled per proposal so that |U| < 2^13, as two fp16 planes (ONE exponent for the 512
+//                                   channels: a channel 2^k below the proposal's largest keeps 2^(k - 37) relative, and a
+//                                   large conv2 column on it brings that back -- measured at the bars up to 2^16, past
+//                                   them from 2^20 on, and there 3-6x worse than the direct conv2, whose H is not summed
+//                                   over a 4 x 4 window first: regress_h2.hip header, DESIGN.md "Numeric domain")
 //   W_p[k][n]   = (G g G^T)[i][j]   g = the 3 x 3 filter of (output n, input k); computed in fp64 at pack time, scaled per
 //                                   output channel to [2^11, 2^12), two fp16 planes
 //   M_p = U_p W_p                   three v_mfma_f32_32x32x16_f16 per product (a1 b0 + a0 b1 + a0 b0), fp32 accumulation

@@ -16,6 +16,7 @@ import torch
 import golden_util as gu
 from oracle import p2p_oracle as orc
 from patch2pix_amd.utils import synthetic
+from stress_inputs import _seeded_conv_weights      # lives beside the other stress generators (octaves: the same spread, run forward)
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hipemu"))
 import emu_lib  # noqa: E402
@@ -105,19 +106,6 @@ def test_regressors_against_reference_golden(mode, emu, sd):
         out = emu_lib.regress(emu, reg, None, p1[:4], p2[:4], props)
         assert (out["matches1"] - torch.from_numpy(g[tag + "_matches"][:n])).abs().max() <= COORD_TOL
         assert (out["probs1"] - torch.from_numpy(g[tag + "_probs"][:n])).abs().max() <= SCORE_TOL
-
-
-def _seeded_conv_weights():
-    """conv1 / conv2 weights of a regressor with per-channel magnitudes over 13 octaves and one channel of zeros each."""
-    rng = np.random.default_rng(20261016)
-    out = []
-    for cin in (518, 512):
-        w = rng.standard_normal((512, cin, 3, 3)).astype(np.float32)
-        w *= np.exp2(rng.integers(-9, 4, (512, 1, 1, 1))).astype(np.float32)
-        out.append(w)
-    out[0][7] = 0.0
-    out[1][300] = 0.0
-    return out
 
 
 # sha256 of what the packers wrote for _seeded_conv_weights().  Recorded from the build of commit 97c98c9 -- the parent of the
