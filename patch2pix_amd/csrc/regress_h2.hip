@@ -16,11 +16,11 @@
 // them is undone exactly by a later multiplication:
 //   * activations of conv1: the per-pixel L2-normalised level-0 values (|v| <= 1) times 2^12; the cells of levels 1, 2 and
 //     3 times 2^e of their image, e = 12 + floor(log2(smallest per-pixel scale)), so that every component is <= 2^12 --
-//     their partial sums are multiplied by scale[pixel] * 2^(12 - e) instead of scale[pixel];
+//     their partial sums are multiplied by scale[pixel] * 2^(12 - e) instead of scale[pixel] (image_exponent, cell_mul, fold_mul);
 //   * weights: per output channel the power of two that brings the largest weight to [2^11, 2^12) (at pack time; folded
 //     into the BatchNorm scale that follows);
 //   * H = BN1(conv1), the input of conv2: per proposal the power of two that brings max |H| to [2^12, 2^13) (a
-//     work-group reduction on the accumulators); BN2's scale is multiplied by its inverse.
+//     work-group reduction on the accumulators: bn1_absmax, h_exponent, h_mul); BN2's scale is multiplied by its inverse (h_inv).
 // Elements more than 2^17 below the largest of their tensor lose relative precision: their second plane becomes an fp16
 // subnormal, absolute error 2^-25 on the scaled value = 2^-37 of the largest, i.e. a relative error of 2^(k - 37) for an
 // element 2^k below it -- one bit per octave.  As an ABSOLUTE error that is far below the rounding of the fp32
@@ -87,7 +87,7 @@ constexpr int XUB = XNPL * 1024;
 // conv1 phase, per image: level 1 as two fp16 planes [plane][9 grid rows (+112 B)][9 cells][64 ch (+16 B pad)]; levels 2 and 3 as
 // two fp16 planes [plane][25 cells + 432 B of zeros][64 ch (+16 B)] and [plane][9 cells + 576 B of zeros][128 ch (+32 B)] ("Bank
 // slots" below).  Then level 0 raw [img][3][256] and one
-// shared region that is, in turn: the fp32 copies of levels 1-3 the scale pass reads (and the planes are converted from); the pre-scaled level-0 im2col
+// shared region that is, in turn: the fp32 copies of levels 1-3 (tmp_cell) the scale pass reads and the planes are converted from; the pre-scaled level-0 im2col
 // block A0[64 px][64 K fp32 (+16 B)] (K = img*32 + tap*3 + c, 27 real per image); the fold buffers
 // T2[8 waves][25 level-2 rows][64 n] and T3[8 waves][9 level-3 rows][64 n] fp32 (the two n-tiles of a wave interleaved).  Then the fold table [img][17][17] of {scale, T row offset} (row/column 0 =
 // the zero padding ring of the convolution) and the per-pixel scale [2][256].
@@ -141,7 +141,7 @@ constexpr int HST = 128 * 2 + 16, HPL = 66 * HST;                 // 272, 17952
 constexpr int HCHUNK = XNPL * HPL;                                // 35904: planes of chunk c start at c * HCHUNK
 constexpr int XCONV2B = 4 * HCHUNK;
 // both phases, then the FC batch of the level (fc_batch_parse) over the whole allocation
-constexpr int XSM_MISC = (XCONV1B > XCONV2B) ? XCONV1B : XCONV2B;  // [16] floats: 8-11 the proposal, 12-14 the fp16 scale reductions
+constexpr int XSM_MISC = (XCONV1B > XCONV2B) ? XCONV1B : XCONV2B;  // [16] floats, the MISC_* slots below
 #ifdef P2P_X3_TIMING
 constexpr int XSM_BYTES = XSM_MISC + 16 * 4 + 8 * 16 * 4;
 #else
@@ -349,6 +349,137 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
       XHMFMAS(AC0, AC1, BC0, BC1)                                                                                     \
       XHPIPE() __builtin_amdgcn_sched_barrier(0); }
 
+// ---- the misc block: [16] floats behind the convolution buffers (XSM_MISC) -------------------------------------------
+enum : int {
+    MISC_NEXT_PROP = 4,                 // 4-7: WINO, (x1, y1, x2, y2) of the proposal this work-group takes next (its gather is prefetched)
+    MISC_PROP = 8,                      // 8-11: (x1, y1, x2, y2) of this proposal
+    MISC_MIN_SCALE = 12,                // 12-13: per image, the smallest per-pixel L2 scale (float bits, atomic min)
+    MISC_MAX_H = 14,                    // the largest |H| = |BN1(conv1)| of the proposal (float bits, atomic max)
+};
+static_assert(MISC_MAX_H == MISC_MIN_SCALE + 2, "the three reductions are reset by three consecutive threads");
+
+// The power-of-two operand scales (file header) are built from the BIASED exponent field of a reduction's float bits: a value
+// with the field eb lies in [2^(eb - 127), 2^(eb - 126)), and the float whose bits are the field k alone is 2^(k - 127).  The
+// clamps bind only for a degenerate reduction (a zero or denormal scale from an infinite sum of squares, an all-zero H, a
+// NaN): whatever it holds, every field derived below stays inside 1 ... 254 with room to spare -- image: eb + 12 <= 252,
+// 254 - eb >= 14; H: 254 + top - eb >= 14, eb - top >= 8 -- so each multiplier is a finite normal power of two and the
+// pair (multiplier, inverse) stays exact.  Ordinary inputs are far inside: a per-pixel scale has eb = 63 ... 136.
+__device__ __forceinline__ int image_exponent(const float *misc, int img) {
+    return clampi((((const int *)misc)[MISC_MIN_SCALE + img] >> 23) & 0xff, 13, 240);
+}
+__device__ __forceinline__ int h_exponent(const float *misc) { return clampi((((const int *)misc)[MISC_MAX_H] >> 23) & 0xff, 20, 250); }
+// image: the cells of levels 1-3 are multiplied by 2^e, e = 12 + (eb - 127) = 12 + floor(log2(smallest per-pixel scale)), so that
+// every component is <= 2^12 (|c| * scale[p] <= 1 for the pixels p of its cell); the fold multiplies by scale[p] * 2^(12 - e)
+__device__ __forceinline__ float cell_mul(int eb) { return __int_as_float((eb + 12) << 23); }
+__device__ __forceinline__ float fold_mul(int eb) { return __int_as_float((254 - eb) << 23); }
+// H: the multiplier that brings max |H| into [2^top, 2^(top + 1)), and its inverse
+__device__ __forceinline__ float h_mul(int eb, int top) { return __int_as_float((254 + top - eb) << 23); }
+__device__ __forceinline__ float h_inv(int eb, int top) { return __int_as_float((eb - top) << 23); }
+
+// ---- gather (networks/utils.py:4-36): the 16 x 16 patch of level 0 and the cell tiles of levels 1-3, both images ---------
+// level j of a patch: cells per side, channels, and 4-byte loads per thread when NT threads share channels x cells^2 elements
+constexpr int level_cells(int j) { return (j == 0) ? 16 : (j == 1) ? 9 : (j == 2) ? 5 : 3; }
+constexpr int level_channels(int j) { return (j == 0) ? 3 : (j == 3) ? 128 : 64; }
+constexpr int level_loads(int j) { return (level_channels(j) * level_cells(j) * level_cells(j) + NT - 1) / NT; }
+// LDS offset of the fp32 copy of cell c of level j (1-3) of image img (the shared region; the scale pass reads it, the planes
+// are converted from it)
+__device__ __forceinline__ int tmp_cell(int img, int j, int c) {
+    return (j == 1) ? XSHARED + XTMP1 + img * XTMP1IMG + c * XTMP1ST
+                    : XSHARED + img * XTMPIMG + ((j == 2) ? c * XTMP2ST : XTMP3 + c * XTMP3ST);
+}
+// the thread id, recomputed from the hardware lane id and opaque: index math derived from it is not hoisted out of the loops
+// around the place the copy is made (and kept, or spilled, across the convolutions)
+__device__ __forceinline__ int opaque_tid(int wave) {
+    int t = wave * 64 + P2P_LANE_ID();
+    P2P_OPAQUE(t);
+    return t;
+}
+// Staging registers: a thread's ~40 scattered loads are all issued before any of them is stored to LDS, so that they are in
+// flight together.  tv = an opaque copy of the thread id (the caller's: the lane-only index math stays where the copy was made).
+struct GatherRegs { float v[2][4][level_loads(1)]; };     // [image][level][load]
+__device__ __forceinline__ void gather_loads(GatherRegs &g, int tv, int xa, int ya, int xb, int yb, const ItemDev &J) {
+#pragma unroll
+    for (int img = 0; img < 2; ++img) {
+        const int Hh = J.H[img], Ww = J.W[img], x0 = img ? xb : xa, y0 = img ? yb : ya;
+        {
+            const int r0 = clampi(y0, 0, Hh - 1), c0 = clampi(x0, 0, Ww - 1);
+            const float *src = J.pyr[img][0];
+#pragma unroll
+            for (int k = 0; k < level_loads(0); ++k) {
+                const int e = tv + k * NT;
+                const int c = e >> 8, rem = e & 255, r = rem >> 4, cc = rem & 15;
+                g.v[img][0][k] = (e < 768) ? src[((size_t)c * Hh + min(r0 + r, Hh - 1)) * Ww + min(c0 + cc, Ww - 1)] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+            const int Rr = level_cells(j);
+            const int Hj = Hh >> j, Wj = Ww >> j;                     // index clamp: dim // ds (networks/utils.py:22-23)
+            const int Ha = level_dim(Hh, j), Wa = level_dim(Ww, j);  // extent of the backbone's map
+            const int r0 = clampi(y0 >> j, 0, Hj - 1);
+            const int c0 = clampi(x0 >> j, 0, Wj - 1);
+            const float *src = J.pyr[img][j];
+#pragma unroll
+            for (int k = 0; k < level_loads(j); ++k) {
+                const int e = tv + k * NT;
+                const int c = e / (Rr * Rr);
+                const int rem = e - c * (Rr * Rr);
+                const int r = rem / Rr;
+                const int cc = rem - r * Rr;
+                g.v[img][j][k] = (e < level_channels(j) * Rr * Rr)
+                                     ? src[((size_t)c * Ha + min(r0 + r, Hj - 1)) * Wa + min(c0 + cc, Wj - 1)] : 0.f;
+            }
+        }
+    }
+}
+// ... -> LDS: level 0 raw [img][3][256], levels 1-3 as fp32 copies (exact: the planes p0 + p1 are split from them)
+__device__ __forceinline__ void gather_commit(const GatherRegs &g, int tv, unsigned char *smb) {
+#pragma unroll
+    for (int img = 0; img < 2; ++img) {
+#pragma unroll
+        for (int k = 0; k < level_loads(0); ++k) {
+            const int e = tv + k * NT;
+            if (e < 768) ((float *)(smb + XRAW0))[img * 768 + e] = g.v[img][0][k];
+        }
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+            const int Rr = level_cells(j);
+#pragma unroll
+            for (int k = 0; k < level_loads(j); ++k) {
+                const int e = tv + k * NT;
+                if (e < level_channels(j) * Rr * Rr) {
+                    const int c = e / (Rr * Rr);
+                    const int rem = e - c * (Rr * Rr);
+                    *(float *)(smb + tmp_cell(img, j, rem) + c * 4) = g.v[img][j][k];
+                }
+            }
+        }
+    }
+}
+// every staging register defined (from an opaque zero, or the constant is kept in a register across the convolutions)
+__device__ __forceinline__ void gather_zero(GatherRegs &g) {
+    float zf = 0.f;
+    P2P_OPAQUE(zf);
+#pragma unroll
+    for (int img = 0; img < 2; ++img)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int k = 0; k < level_loads(j); ++k) g.v[img][j][k] = zf;
+}
+
+// scratch in global memory: pooled features V [level][n][512], then the un-truncated matches of the previous level [n][4]
+// (macros over the launch arguments, re-derived where they are used: two more live 64-bit pointers across the convolution
+// phases spill)
+#define XWS_V(lvl_) (args.ws + (size_t)(lvl_) * args.n * 512)
+#define XWS_NEXTP() (args.ws + ((2 * (size_t)args.n * 512 + 31) & ~(size_t)31))
+// coordinate q of proposal slot `prop` at level lvl: the caller's proposals, or the previous level's regressed matches
+__device__ __forceinline__ float proposal_coord(const RegressArgs &args, int lvl, int prop, int q) {
+    if (lvl > 0) return load_coherent(XWS_NEXTP() + (size_t)prop * 4 + q);
+    if (args.is_float) return ((const float *)args.proposals)[(size_t)prop * 4 + q];
+    return (float)((const long long *)args.proposals)[(size_t)prop * 4 + q];
+}
+
 // Persistent work-groups: the launch has min(n, compute units) of them (one fits a compute unit), work-group g owns the
 // proposals g, g + G, g + 2G, ...  Per level it runs the two convolutions of each of its proposals (pooled features V[512]
 // -> global scratch), then the FC tail of ALL of them as one batch (fc_batch_parse: weights streamed once per 16
@@ -366,87 +497,14 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
     float *raw0 = (float *)(smb + XRAW0);
     float *scale = (float *)(smb + XSM_SCALE);
     float *misc = (float *)(smb + XSM_MISC);
-    // scratch (re-derived from the launch arguments where it is used: two more live 64-bit pointers across the convolution
-    // phases spill): pooled features V [level][n][512], then the un-truncated matches of the previous level [n][4]
-#define XWS_V(lvl_) (args.ws + (size_t)(lvl_) * args.n * 512)
-#define XWS_NEXTP() (args.ws + ((2 * (size_t)args.n * 512 + 31) & ~(size_t)31))
 
 #pragma unroll 1
     for (int lvl = WINO ? args.lvl0 : 0; lvl < (WINO ? args.lvl0 + 1 : args.nlevels); ++lvl) {
         const RegDev &R_ = args.reg[lvl];
         // WINO: the gather of proposal i + 1 is issued before the transform + write-out of proposal i (its ~40 scattered loads
         // per thread land in these registers while that phase runs) and committed to LDS at the top of its own iteration
-        float gn0[2][2], gn1[2][11], gn2[2][4], gn3[2][3];
-        bool pre = false;                    // gn* hold the gather of the proposal the next iteration starts with
-        auto gather_loads = [&](int xa_, int ya_, int xb_, int yb_, const ItemDev &J) {
-            int tv = wave * 64 + P2P_LANE_ID();
-            P2P_OPAQUE(tv);
-#pragma unroll
-            for (int img = 0; img < 2; ++img) {
-                const int Hh = J.H[img], Ww = J.W[img], x0 = img ? xb_ : xa_, y0 = img ? yb_ : ya_;
-                {
-                    const int r0 = clampi(y0, 0, Hh - 1), c0 = clampi(x0, 0, Ww - 1);
-                    const float *src = J.pyr[img][0];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int e = tv + k * NT;
-                        const int c = e >> 8, rem = e & 255, r = rem >> 4, cc = rem & 15;
-                        gn0[img][k] = (e < 768) ? src[((size_t)c * Hh + min(r0 + r, Hh - 1)) * Ww + min(c0 + cc, Ww - 1)] : 0.f;
-                    }
-                }
-#pragma unroll
-                for (int j = 1; j < 4; ++j) {
-                    const int Rr = (j == 1) ? 9 : (j == 2) ? 5 : 3;
-                    const int Cc = (j == 3) ? 128 : 64;
-                    const int nk = (j == 1) ? 11 : (j == 2) ? 4 : 3;
-                    const int Hj = Hh >> j, Wj = Ww >> j;
-                    const int Ha = level_dim(Hh, j), Wa = level_dim(Ww, j);
-                    const int r0 = clampi(y0 >> j, 0, Hj - 1);
-                    const int c0 = clampi(x0 >> j, 0, Wj - 1);
-                    const float *src = J.pyr[img][j];
-#pragma unroll
-                    for (int k = 0; k < nk; ++k) {
-                        const int e = tv + k * NT;
-                        const int c = e / (Rr * Rr);
-                        const int rem = e - c * (Rr * Rr);
-                        const int r = rem / Rr;
-                        const int cc = rem - r * Rr;
-                        const float v = (e < Cc * Rr * Rr)
-                                            ? src[((size_t)c * Ha + min(r0 + r, Hj - 1)) * Wa + min(c0 + cc, Wj - 1)] : 0.f;
-                        if (j == 1) gn1[img][k] = v; else if (j == 2) gn2[img][k] = v; else gn3[img][k] = v;
-                    }
-                }
-            }
-        };
-        auto gather_commit = [&]() {
-            int tv = wave * 64 + P2P_LANE_ID();
-            P2P_OPAQUE(tv);
-#pragma unroll
-            for (int img = 0; img < 2; ++img) {
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int e = tv + k * NT;
-                    if (e < 768) raw0[img * 768 + e] = gn0[img][k];
-                }
-#pragma unroll
-                for (int j = 1; j < 4; ++j) {
-                    const int Rr = (j == 1) ? 9 : (j == 2) ? 5 : 3;
-                    const int Cc = (j == 3) ? 128 : 64;
-                    const int nk = (j == 1) ? 11 : (j == 2) ? 4 : 3;
-#pragma unroll
-                    for (int k = 0; k < nk; ++k) {
-                        const int e = tv + k * NT;
-                        if (e < Cc * Rr * Rr) {
-                            const int c = e / (Rr * Rr);
-                            const int rem = e - c * (Rr * Rr);
-                            const float v = (j == 1) ? gn1[img][k] : (j == 2) ? gn2[img][k] : gn3[img][k];
-                            if (j == 1) *(float *)(smb + XSHARED + XTMP1 + img * XTMP1IMG + rem * XTMP1ST + c * 4) = v;
-                            else *(float *)(smb + XSHARED + img * XTMPIMG + ((j == 2) ? rem * XTMP2ST : XTMP3 + rem * XTMP3ST) + c * 4) = v;
-                        }
-                    }
-                }
-            }
-        };
+        GatherRegs gn;
+        bool pre = false;                    // gn holds the gather of the proposal the next iteration starts with
 #pragma unroll 1
       for (int cprop = (WINO ? args.p0 : 0) + blockIdx.x; cprop < (WINO ? args.p1 : args.n); cprop += nwg) {
         // WINO: cprop is the compact index of a proposal that exists (its scratch rows), prop its slot; else they coincide
@@ -457,45 +515,30 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
         if (!WINO && args.dev_counts && prop - args.start[it] >= args.dev_counts[it]) continue;      // empty slot (whole work-group)
         const ItemDev &I = args.item[it];
         int tq = tid;                        // WINO: an opaque copy -- the lane's load addresses are otherwise hoisted out of the loop and spilled
-        if constexpr (WINO) {
-            tq = wave * 64 + P2P_LANE_ID();
-            P2P_OPAQUE(tq);
-        }
+        if constexpr (WINO) tq = opaque_tid(wave);
         if (tq < 4) {
-            float v;
-            if (lvl > 0) v = load_coherent(XWS_NEXTP() + (size_t)prop * 4 + tq);
-            else if (args.is_float) v = ((const float *)args.proposals)[(size_t)prop * 4 + tq];
-            else v = (float)((const long long *)args.proposals)[(size_t)prop * 4 + tq];
+            float v = proposal_coord(args, lvl, prop, tq);
 #ifdef XF_SAME_PATCH                    // timing experiment (wrong results): every proposal gathers the same (cache-resident) patch
             v = 100.f + 16.f * tq;
 #endif
-            misc[8 + tq] = v;
+            misc[MISC_PROP + tq] = v;
         }
-        if constexpr (WINO) {                // the proposal this work-group takes next (its gather is prefetched): coordinates -> misc[4..7]
+        if constexpr (WINO) {                // the proposal this work-group takes next (its gather is prefetched)
             const int nprop = (cprop + nwg < args.p1) ? wino_slot(args, cprop + nwg) : -1;
-            if (nprop >= 0 && tq >= 4 && tq < 8) {
-                const int q = tq - 4;
-                float v;
-                if (lvl > 0) v = load_coherent(XWS_NEXTP() + (size_t)nprop * 4 + q);
-                else if (args.is_float) v = ((const float *)args.proposals)[(size_t)nprop * 4 + q];
-                else v = (float)((const long long *)args.proposals)[(size_t)nprop * 4 + q];
-                misc[4 + q] = v;
-            }
+            if (nprop >= 0 && tq >= 4 && tq < 8) misc[MISC_NEXT_PROP + tq - 4] = proposal_coord(args, lvl, nprop, tq - 4);
         }
-        // per-level reductions behind the power-of-two operand scales: misc[12 + img] = smallest per-pixel L2 scale of the
-        // image (float bits, atomic min), misc[14] = largest |H| (float bits, atomic max)
-        if (tq >= 64 && tq < 67) ((int *)misc)[12 + tq - 64] = (tq < 66) ? 0x7f7fffff : 0;
+        // the per-proposal reductions behind the power-of-two operand scales: two minima, one maximum
+        if (tq >= 64 && tq < 67) ((int *)misc)[MISC_MIN_SCALE + tq - 64] = (tq < 66) ? 0x7f7fffff : 0;
         __syncthreads();
         // window origins (x, y) in image 1 / image 2 (networks/utils.py:8-19); scalars + selects, never an indexed array
-        int moff = 8;                // opaque: the LDS address of misc is otherwise materialised before the loop and spilled
+        int moff = MISC_PROP;        // opaque: the LDS address of misc is otherwise materialised before the loop and spilled
         P2P_OPAQUE(moff);
         const int xa = (int)misc[moff + 0] - 8, ya = (int)misc[moff + 1] - 8;
         const int xb = (int)misc[moff + 2] - 8, yb = (int)misc[moff + 3] - 8;
 #define XX0(img_) ((img_) ? xb : xa)
 #define XY0(img_) ((img_) ? yb : ya)
         // opaque copy of the thread id for the staging phases (keeps their lane-only index math inside the level loop)
-        int tidv = wave * 64 + P2P_LANE_ID();       // re-derived per level: not even the thread id is kept in a VGPR across it
-        P2P_OPAQUE(tidv);
+        const int tidv = opaque_tid(wave);          // re-derived per proposal: not even the thread id is kept in a VGPR across it
         // lane coordinates derived from the opaque copy: nothing lane-dependent is loop-invariant for the compiler, so
         // nothing is hoisted out of the level loop and kept (or spilled) across its high-pressure phases
         const int half = (tidv >> 5) & 1, l31 = tidv & 31;
@@ -504,78 +547,16 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
         // ~20 % slower between barriers): static priority for that half, no per-segment flips
         if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 
-        // ------------------------------------------------------------ gather (networks/utils.py:4-36)
+        // ------------------------------------------------------------ gather
         if constexpr (WINO) {
-            if (!pre) gather_loads(xa, ya, xb, yb, I);       // the work-group's first proposal: nothing was prefetched
-            gather_commit();
+            // the work-group's first proposal: nothing was prefetched.  A fresh opaque thread id per use: one made from tidv
+            // would be kept across conv1 for the prefetch
+            if (!pre) gather_loads(gn, opaque_tid(wave), xa, ya, xb, yb, I);
+            gather_commit(gn, opaque_tid(wave), smb);
         } else {
-            // two passes so that all ~40 scattered 4-byte loads of a thread are in flight together
-            float g0[2][2], g1[2][11], g2[2][4], g3[2][3];
-#pragma unroll
-            for (int img = 0; img < 2; ++img) {
-                const int Hh = I.H[img], Ww = I.W[img];
-                {
-                    const int r0 = clampi(XY0(img), 0, Hh - 1), c0 = clampi(XX0(img), 0, Ww - 1);
-                    const float *src = I.pyr[img][0];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int e = tidv + k * NT;
-                        const int c = e >> 8, rem = e & 255, r = rem >> 4, cc = rem & 15;
-                        g0[img][k] = (e < 768) ? src[((size_t)c * Hh + min(r0 + r, Hh - 1)) * Ww + min(c0 + cc, Ww - 1)] : 0.f;
-                    }
-                }
-#pragma unroll
-                for (int j = 1; j < 4; ++j) {
-                    const int Rr = (j == 1) ? 9 : (j == 2) ? 5 : 3;
-                    const int Cc = (j == 3) ? 128 : 64;
-                    const int nk = (j == 1) ? 11 : (j == 2) ? 4 : 3;
-                    const int Hj = Hh >> j, Wj = Ww >> j;                     // index clamp: dim // ds (networks/utils.py:22-23)
-                    const int Ha = level_dim(Hh, j), Wa = level_dim(Ww, j);  // extent of the backbone's map
-                    const int r0 = clampi(XY0(img) >> j, 0, Hj - 1);
-                    const int c0 = clampi(XX0(img) >> j, 0, Wj - 1);
-                    const float *src = I.pyr[img][j];
-#pragma unroll
-                    for (int k = 0; k < nk; ++k) {
-                        const int e = tidv + k * NT;
-                        const int c = e / (Rr * Rr);
-                        const int rem = e - c * (Rr * Rr);
-                        const int r = rem / Rr;
-                        const int cc = rem - r * Rr;
-                        const float v = (e < Cc * Rr * Rr)
-                                            ? src[((size_t)c * Ha + min(r0 + r, Hj - 1)) * Wa + min(c0 + cc, Wj - 1)] : 0.f;
-                        if (j == 1) g1[img][k] = v; else if (j == 2) g2[img][k] = v; else g3[img][k] = v;
-                    }
-                }
-            }
-#pragma unroll
-            for (int img = 0; img < 2; ++img) {
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int e = tidv + k * NT;
-                    if (e < 768) raw0[img * 768 + e] = g0[img][k];
-                }
-#pragma unroll
-                for (int j = 1; j < 4; ++j) {
-                    const int Rr = (j == 1) ? 9 : (j == 2) ? 5 : 3;
-                    const int Cc = (j == 3) ? 128 : 64;
-                    const int nk = (j == 1) ? 11 : (j == 2) ? 4 : 3;
-#pragma unroll
-                    for (int k = 0; k < nk; ++k) {
-                        const int e = tidv + k * NT;
-                        if (e < Cc * Rr * Rr) {
-                            const int c = e / (Rr * Rr);
-                            const int rem = e - c * (Rr * Rr);
-                            const float v = (j == 1) ? g1[img][k] : (j == 2) ? g2[img][k] : g3[img][k];
-                            if (j == 1) {
-                                *(float *)(smb + XSHARED + XTMP1 + img * XTMP1IMG + rem * XTMP1ST + c * 4) = v;
-                            } else {
-                                // fp32 copy for the scale pass + the planes (exact: v = p0 + p1)
-                                *(float *)(smb + XSHARED + img * XTMPIMG + ((j == 2) ? rem * XTMP2ST : XTMP3 + rem * XTMP3ST) + c * 4) = v;
-                            }
-                        }
-                    }
-                }
-            }
+            GatherRegs g;
+            gather_loads(g, tidv, xa, ya, xb, yb, I);
+            gather_commit(g, tidv, smb);
         }
         if (tidv < 2 * XNPL * (3 * YST2 + 2 * YST3) / 16) {  // the zero areas: the dead rows of the cell tiles multiply zeros
             const int per = (3 * YST2 + 2 * YST3) / 16;
@@ -603,13 +584,9 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
             const int c2 = patch_cell(XY0(img), py, 2, I.H[img]) * 5 + patch_cell(XX0(img), px, 2, I.W[img]);
 #pragma unroll
             for (int j = 1; j < 4; ++j) {
-                const int Rr = (j == 1) ? 9 : (j == 2) ? 5 : 3;
-                const int Cc = (j == 3) ? 128 : 64;
                 const int cjy = patch_cell(XY0(img), py, j, I.H[img]), cjx = patch_cell(XX0(img), px, j, I.W[img]);
-                const int cj = cjy * Rr + cjx;
-                const unsigned char *p = (j == 1) ? smb + XSHARED + XTMP1 + img * XTMP1IMG + cj * XTMP1ST
-                                                  : smb + XSHARED + img * XTMPIMG + ((j == 2) ? cj * XTMP2ST : XTMP3 + cj * XTMP3ST);
-                for (int c = 0; c < Cc; c += 4) {
+                const unsigned char *p = smb + tmp_cell(img, j, cjy * level_cells(j) + cjx);
+                for (int c = 0; c < level_channels(j); c += 4) {
                     const f32x4 v = *(const f32x4 *)(p + c * 4);
                     ss = fmaf(v[0], v[0], ss); ss = fmaf(v[1], v[1], ss); ss = fmaf(v[2], v[2], ss); ss = fmaf(v[3], v[3], ss);
                 }
@@ -618,7 +595,7 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
             // fp16 operands carry power-of-two scales (header): per-pixel-normalised values x 2^12; the fold table entry
             // needs the image's smallest scale and is written after the barrier
             scale[tidv] = sc * 4096.0f;
-            atomicMin((int *)misc + 12 + img, __float_as_int(sc));
+            atomicMin((int *)misc + MISC_MIN_SCALE + img, __float_as_int(sc));
             sc_keep = sc;
             c23_keep = c2 * XTROW | (patch_cell(XY0(img), py, 3, I.H[img]) * 3 + patch_cell(XX0(img), px, 3, I.W[img])) * XTROW << 16;
             if (tidv < 2 * 33) {     // ring = the zero padding of conv1: scale 0
@@ -630,22 +607,19 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
             }
         }
         __syncthreads();
-        {   // the image's power-of-two scale 2^e, e = 12 + floor(log2(smallest per-pixel scale)): every cell component
-            // times 2^e is <= 2^12 (|c| * scale[p] <= 1 for the pixels p of its cell), the fold multiplies by scale[p] * 2^(12 - e)
+        {   // the image's power-of-two scale 2^e (cell_mul / fold_mul) is known: the pixel's fold table entry
             const int img = tidv >> 8, pix = tidv & 255, py = pix >> 4, px = pix & 15;
-            const int eb = clampi((((const int *)misc)[12 + img] >> 23) & 0xff, 13, 240);
             *(f32x2 *)(smb + XTAB + img * XTABIMG + ((py + 1) * 17 + px + 1) * 8) =
-                (f32x2){sc_keep * __int_as_float((254 - eb) << 23), __int_as_float(c23_keep)};
+                (f32x2){sc_keep * fold_mul(image_exponent(misc, img)), __int_as_float(c23_keep)};
             // planes of levels 1, 2 and 3 from their fp32 copies.  Level 1: 2 x 81 x 32 channel PAIRS (one 4-byte store per plane)
 #pragma unroll
             for (int k = 0; k < 11; ++k) {
                 const int e = tidv + k * NT;
                 if (e < 2 * 2592) {
                     const int im = (e >= 2592), r = e - im * 2592;
-                    const int ebi = clampi((((const int *)misc)[12 + im] >> 23) & 0xff, 13, 240);
-                    const float mul = __int_as_float((ebi + 12) << 23);
+                    const float mul = cell_mul(image_exponent(misc, im));
                     const int cell = r >> 5, c2 = (r & 31) * 2, cy = cell / 9, cx = cell - 9 * cy;
-                    const f32x2 v = *(const f32x2 *)(smb + XSHARED + XTMP1 + im * XTMP1IMG + cell * XTMP1ST + c2 * 4);
+                    const f32x2 v = *(const f32x2 *)(smb + tmp_cell(im, 1, cell) + c2 * 4);
                     const unsigned h = pk_e(v[0] * mul, v[1] * mul);
                     unsigned char *d = smb + im * XIMG + XOFF1 + cy * XRP1 + cx * XST1 + c2 * 2;
                     *(unsigned *)d = h;
@@ -658,11 +632,10 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
                 const int e = tidv + k * NT;
                 if (e < 2 * 2752) {
                     const int im = (e >= 2752), r = e - im * 2752;
-                    const int ebi = clampi((((const int *)misc)[12 + im] >> 23) & 0xff, 13, 240);
-                    const float mul = __int_as_float((ebi + 12) << 23);
+                    const float mul = cell_mul(image_exponent(misc, im));
                     const bool l2 = r < 1600;
                     const int cell = l2 ? r >> 6 : (r - 1600) >> 7, c = l2 ? r & 63 : (r - 1600) & 127;
-                    const float v = *(const float *)(smb + XSHARED + im * XTMPIMG + (l2 ? cell * XTMP2ST : XTMP3 + cell * XTMP3ST) + c * 4);
+                    const float v = *(const float *)(smb + tmp_cell(im, l2 ? 2 : 3, cell) + c * 4);
                     store_planes(smb + im * XIMG + (l2 ? YOFF2 + cell * YST2 : YOFF3 + cell * YST3) + c * 2, l2 ? YPL2 : YPL3, v * mul);
                 }
             }
@@ -693,6 +666,24 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
         XZERO16(acc00) XZERO16(acc01) XZERO16(acc10) XZERO16(acc11)
         f32x4 B0[XNPL], B1[XNPL], B2[XNPL], B3[XNPL], B4[XNPL], B5[XNPL], B6[XNPL], B7[XNPL], S0[XNPL], S1[XNPL];
         const f32x16 zero16 = {0};
+        // accumulator of m-tile t (pixels 32 t ...), n-tile u (channels 64 wave + 32 u + l31)
+        auto acc_tile = [&](int t, int u) -> const f32x16 & { return (t == 0) ? (u == 0 ? acc00 : acc01) : (u == 0 ? acc10 : acc11); };
+        // max |H| of the proposal, H = BN1(conv1), -> misc[MISC_MAX_H] (h_exponent, after a barrier)
+        auto bn1_absmax = [&]() {
+            float mx = 0.f;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int n = wave * 64 + u * 32 + l31;
+                const float s = R_.bn1s_h[n], b = R_.bn1b[n];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const f32x16 &a = acc_tile(t, u);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, fabsf(fmaf(a[r], s, b)));
+                }
+            }
+            atomicMax((int *)misc + MISC_MAX_H, __float_as_int(mx));
+        };
         {
             f32x4 R0[2], R1[2];
             const unsigned char *wb = (const unsigned char *)R_.wh1 + (size_t)wave * (S1_UNITS + XPF) * XUB;
@@ -865,21 +856,7 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
             // wino_gemm_kernel: [position 16][row block][K chunk 16][plane 2][row 128][4 pieces of 8 ch, XOR-swizzled].
             constexpr int HWST = 512 * 4 + 16;
             static_assert(65 * HWST <= XSM_MISC, "H as fp32 fits the convolution buffers");
-            {
-                float mx = 0.f;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int n = wave * 64 + u * 32 + l31;
-                    const float s = R_.bn1s_h[n], b = R_.bn1b[n];
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        const f32x16 &a = (t == 0) ? (u == 0 ? acc00 : acc01) : (u == 0 ? acc10 : acc11);
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, fabsf(fmaf(a[r], s, b)));
-                    }
-                }
-                atomicMax((int *)misc + 14, __float_as_int(mx));
-            }
+            bn1_absmax();
             if (tidv < HWST / 16) {
                 float zf = 0.f;
                 P2P_OPAQUE(zf);
@@ -887,16 +864,16 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
             }
             __syncthreads();
             // |H| * hmul in [2^10, 2^11): the transform grows a value at most fourfold, |U| < 2^13
-            const int eb = clampi((((const int *)misc)[14] >> 23) & 0xff, 20, 250);
-            const float hmul = __int_as_float((264 - eb) << 23);
-            if (tidv == 0) args.hinv[cprop - args.p0] = __int_as_float((eb - 10) << 23);
+            const int eb = h_exponent(misc);
+            const float hmul = h_mul(eb, 10);
+            if (tidv == 0) args.hinv[cprop - args.p0] = h_inv(eb, 10);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int n = wave * 64 + u * 32 + l31;
                 const float s = R_.bn1s_h[n], b = R_.bn1b[n];
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    const f32x16 &a = (t == 0) ? (u == 0 ? acc00 : acc01) : (u == 0 ? acc10 : acc11);
+                    const f32x16 &a = acc_tile(t, u);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int p = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * half;
@@ -913,25 +890,14 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
             if (pre) {
                 int nit = 0;
                 while (nit + 1 < args.nitems && nprop2 >= args.start[nit + 1]) ++nit;
-                int mo2 = 4;
+                int mo2 = MISC_NEXT_PROP;
                 P2P_OPAQUE(mo2);
-                gather_loads((int)misc[mo2 + 0] - 8, (int)misc[mo2 + 1] - 8, (int)misc[mo2 + 2] - 8, (int)misc[mo2 + 3] - 8, args.item[nit]);
+                gather_loads(gn, opaque_tid(wave), (int)misc[mo2 + 0] - 8, (int)misc[mo2 + 1] - 8, (int)misc[mo2 + 2] - 8, (int)misc[mo2 + 3] - 8,
+                             args.item[nit]);
             } else {
                 // (defined on this path too: otherwise the values committed at the top of this iteration count as live across
                 // conv1 -- the compiler does not see that `pre == false` makes the next iteration reload them -- 40 registers)
-                float zf = 0.f;
-                P2P_OPAQUE(zf);
-#pragma unroll
-                for (int im = 0; im < 2; ++im) {
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) gn0[im][k] = zf;
-#pragma unroll
-                    for (int k = 0; k < 11; ++k) gn1[im][k] = zf;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) gn2[im][k] = zf;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) gn3[im][k] = zf;
-                }
+                gather_zero(gn);
             }
             // item = K chunk of 32 channels: lane = (tile, 8 channels), two passes of 4 channels; a lane's 8 values of a
             // (position, plane) are ONE 16-byte store and a wave's store covers the proposal's 16 rows of a block = 1 KiB
@@ -1003,23 +969,9 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
             }
             const int chunk = wave >> 1;
             // H is scaled by the power of two that brings its largest magnitude to [2^12, 2^13) before it is split
-            {
-                float mx = 0.f;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int n = wave * 64 + u * 32 + l31;
-                    const float s = R_.bn1s_h[n], b = R_.bn1b[n];
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        const f32x16 &a = (t == 0) ? (u == 0 ? acc00 : acc01) : (u == 0 ? acc10 : acc11);
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, fabsf(fmaf(a[r], s, b)));
-                    }
-                }
-                atomicMax((int *)misc + 14, __float_as_int(mx));
-            }
+            bn1_absmax();
             __syncthreads();
-            const float hmul = __int_as_float((266 - clampi((((const int *)misc)[14] >> 23) & 0xff, 20, 250)) << 23);
+            const float hmul = h_mul(h_exponent(misc), 12);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int n = wave * 64 + u * 32 + l31;
@@ -1031,7 +983,7 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
                 unsigned char *dplane = smb + chunk * HCHUNK + (odd ? HPL : 0) + 4 * half * HST + (cc & ~1) * 2;
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    const f32x16 &a = (t == 0) ? (u == 0 ? acc00 : acc01) : (u == 0 ? acc10 : acc11);
+                    const f32x16 &a = acc_tile(t, u);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int p = 32 * t + (r & 3) + 8 * (r >> 2);       // + 4 * half
@@ -1110,9 +1062,8 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int n = wave * 64 + u * 32 + l31;
-                const float s = R_.bn2s_h[n] * __int_as_float((clampi((((const int *)misc)[14] >> 23) & 0xff, 20, 250) - 12) << 23), b = R_.bn2b[n];
-                const f32x16 &aa = (u == 0) ? acc00 : acc01;
-                const f32x16 &ab2 = (u == 0) ? acc10 : acc11;
+                const float s = R_.bn2s_h[n] * h_inv(h_exponent(misc), 12), b = R_.bn2b[n];       // undoes h_mul(., 12)
+                const f32x16 &aa = acc_tile(0, u), &ab2 = acc_tile(1, u);
                 float m = 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
