@@ -59,7 +59,8 @@ int p2p_ncn_set_tile(p2p_ncn *ncn, int ta, int tb, int tc);
 
 /* FeatRegressNet with the released configuration (conv_kers [3,3], conv_strs [2,1],
  * conv_dims [512,512], fc_dims [512,256], feat_comb 'pre', psize 16, feat_idx [0,1,2,3]) --
- * reference networks/modules.py:56-112.  HOST pointers to the state_dict tensors.           */
+ * reference networks/modules.py:56-112.  HOST pointers to the state_dict tensors.  These handles run the tuned kernels
+ * (the modes below); every other configuration goes through p2p_regressor_create_config.     */
 typedef struct p2p_bn_params {
     const float *weight, *bias, *running_mean, *running_var;
 } p2p_bn_params;
@@ -101,6 +102,49 @@ void p2p_regressor_destroy(p2p_regressor *reg);
 #define P2P_REGRESS_DEFAULT P2P_REGRESS_FP16X2W
 int p2p_regressor_set_mode(p2p_regressor *reg, int mode);
 int p2p_regressor_get_mode(const p2p_regressor *reg);
+
+/* FeatRegressNet with ANY configuration within the limits below (since version 104): what the reference's training script
+ * stores as `feat_idx` / `regressor_config` of a checkpoint (utils/eval/model_helper.py:28-62).  Such a GENERIC handle runs
+ * a second, shape-generic set of kernels behind the same p2p_regress* entry points: exact fp32 on the matrix cores
+ * (v_mfma_f32_32x32x2_f32 for the convolutions as implicit GEMMs, v_mfma_f32_16x16x4_f32 for the FC tail), one launch per
+ * layer over a chunk of proposals.  Every output's summation order depends on the configuration alone: a proposal's raw
+ * outputs are bit-identical alone, in any batch, with device-side counts and under any chunk size.
+ *   feat_idx   n_feat in [1,4] strictly ascending levels out of {0,1,2,3} (3 / 64 / 64 / 128 channels, strides 1 / 2 / 4 / 8);
+ *              the per-pixel L2 norm runs over the selected channels.  Level 4 -> P2P_EUNSUPPORTED (p2p_pyramid has 4 levels)
+ *   feat_comb  P2P_FEAT_COMB_PRE: one conv stack on cat(f1, f2); P2P_FEAT_COMB_POST: the stack on each image's patch, the
+ *              two pooled vectors concatenated (fc input = 2 conv_dim[n_conv - 1])
+ *   conv       n_conv in [1,4] layers Conv2d(kernel conv_ker in {1,3,5}, stride conv_str in {1,2}, padding 1, no bias) +
+ *              BatchNorm2d; ONE ReLU after the last BatchNorm, then the maximum over the final map.  conv_dim: multiples of
+ *              16 in [16,1024].  A map that would shrink below 1x1 -> P2P_EINVAL
+ *   fc         n_fc in [0,4] hidden layers Linear + BatchNorm1d + ReLU, fc_dim multiples of 16 in [16,1024]; then Linear to 5
+ *   psize      16 (anything else -> P2P_EUNSUPPORTED)
+ * Kernel sizes, strides, dims or layer counts outside these lists -> P2P_EUNSUPPORTED; malformed arguments (null pointers,
+ * counts or dims <= 0, feat_idx out of order) -> P2P_EINVAL.  The released configuration is accepted too (that is how the
+ * generic path is compared with the tuned one); p2p_regressor_create keeps producing tuned handles.
+ * Tensors: HOST pointers to the state_dict tensors, conv_w[i] = conv.{2i}.weight [conv_dim[i], c_in, k, k] (c_in of layer 0:
+ * the selected channels, twice for 'pre'), conv_bn[i] = conv.{2i+1}.*, fc_w/fc_b[i] = fc.{3i}.*, fc_bn[i] = fc.{3i+1}.*,
+ * out_w/out_b = fc.{3 n_fc}.* [5, k], [5].                                                                          */
+#define P2P_FEAT_COMB_PRE  0
+#define P2P_FEAT_COMB_POST 1
+typedef struct p2p_regressor_config {
+    int n_feat, feat_idx[4];
+    int feat_comb;
+    int n_conv, conv_dim[4], conv_ker[4], conv_str[4];
+    int n_fc, fc_dim[4];
+    int psize;
+} p2p_regressor_config;
+typedef struct p2p_regressor_tensors {
+    const float *conv_w[4];
+    p2p_bn_params conv_bn[4];
+    const float *fc_w[4], *fc_b[4];
+    p2p_bn_params fc_bn[4];
+    const float *out_w, *out_b;
+} p2p_regressor_tensors;
+int p2p_regressor_create_config(const p2p_regressor_config *config, const p2p_regressor_tensors *tensors, p2p_regressor **out);
+/* The mode id of a generic handle: p2p_regressor_get_mode returns it, p2p_regressor_set_mode accepts only it on a generic
+ * handle and refuses it on a tuned one (P2P_EUNSUPPORTED both ways).  In p2p_regress* reg1 and reg2 must be of the same kind,
+ * and two generic handles must have equal configurations (P2P_EINVAL otherwise).                                      */
+#define P2P_REGRESS_GENERIC 16
 
 /* ---- coarse stage ---------------------------------------------------------------------------- */
 
@@ -214,6 +258,15 @@ size_t p2p_regress_workspace_bytes(int n);
  *                      mode should size their buffer with this query, not with p2p_regress_workspace_bytes),
  * P2P_REGRESS_FP16X2   4 KB per proposal slot,   P2P_REGRESS_F32   0 (the buffer is ignored).                      */
 size_t p2p_regress_workspace_bytes_mode(int n, int mode);
+/* The same for ONE handle.  Tuned handles: the value of p2p_regress_workspace_bytes_mode for the handle's mode.  Generic
+ * handles: the scratch of one chunk of min(n, 256) proposals rounded up to whole units of 8, per proposal
+ *   4 (mid matches) + fc_in (pooled features) + 2 max(fc_dim) + the largest activation a layer reads + the largest it writes
+ * floats, activations counted as spp x h x w x channels (spp = 2 samples per proposal for 'post', 1 for 'pre'; layer 0
+ * reads 16 x 16 x the selected channels padded to a multiple of 8).  Released configuration: 669 712 bytes per proposal,
+ * 171 MB at the cap of 256.  p2p_regress* derive their chunk from the workspace_bytes they are given -- the largest
+ * multiple of 8 proposals that fits, at most the cap -- and return P2P_ENOMEM below one unit of 8; results do not depend
+ * on the chunk.                                                                                                     */
+size_t p2p_regress_workspace_bytes_for(const p2p_regressor *reg, int n);
 int p2p_regress(const p2p_regressor *reg1, const p2p_regressor *reg2,
                 const p2p_pyramid *im1, const p2p_pyramid *im2,
                 const void *proposals, int is_float, int n,

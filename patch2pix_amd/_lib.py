@@ -43,6 +43,18 @@ class RegressorParams(ctypes.Structure):
                 ("fc3_w", ctypes.c_void_p), ("fc3_b", ctypes.c_void_p)]
 
 
+class RegressorConfig(ctypes.Structure):
+    _fields_ = [("n_feat", ctypes.c_int), ("feat_idx", ctypes.c_int * 4), ("feat_comb", ctypes.c_int),
+                ("n_conv", ctypes.c_int), ("conv_dim", ctypes.c_int * 4), ("conv_ker", ctypes.c_int * 4),
+                ("conv_str", ctypes.c_int * 4), ("n_fc", ctypes.c_int), ("fc_dim", ctypes.c_int * 4), ("psize", ctypes.c_int)]
+
+
+class RegressorTensors(ctypes.Structure):
+    _fields_ = [("conv_w", ctypes.c_void_p * 4), ("conv_bn", BnParams * 4),
+                ("fc_w", ctypes.c_void_p * 4), ("fc_b", ctypes.c_void_p * 4), ("fc_bn", BnParams * 4),
+                ("out_w", ctypes.c_void_p), ("out_b", ctypes.c_void_p)]
+
+
 class Pyramid(ctypes.Structure):
     _fields_ = [("level", ctypes.c_void_p * 4), ("height", ctypes.c_int), ("width", ctypes.c_int)]
 
@@ -65,6 +77,9 @@ p2p_ncn_destroy = _sig("p2p_ncn_destroy", None, [ctypes.c_void_p])
 p2p_ncn_set_tile = _sig("p2p_ncn_set_tile", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3)
 p2p_regressor_create = _sig("p2p_regressor_create", ctypes.c_int,
                             [ctypes.POINTER(RegressorParams), ctypes.POINTER(ctypes.c_void_p)])
+p2p_regressor_create_config = _sig("p2p_regressor_create_config", ctypes.c_int,
+                                   [ctypes.POINTER(RegressorConfig), ctypes.POINTER(RegressorTensors),
+                                    ctypes.POINTER(ctypes.c_void_p)])
 p2p_regressor_destroy = _sig("p2p_regressor_destroy", None, [ctypes.c_void_p])
 p2p_coarse_workspace_bytes = _sig("p2p_coarse_workspace_bytes", ctypes.c_size_t, [ctypes.c_int] * 6)
 p2p_coarse_forward = _sig("p2p_coarse_forward", ctypes.c_int,
@@ -95,6 +110,7 @@ p2p_regress = _sig("p2p_regress", ctypes.c_int,
                     ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_void_p, ctypes.c_size_t, c_stream])
 p2p_regress_workspace_bytes = _sig("p2p_regress_workspace_bytes", ctypes.c_size_t, [ctypes.c_int])
 p2p_regress_workspace_bytes_mode = _sig("p2p_regress_workspace_bytes_mode", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int])
+p2p_regress_workspace_bytes_for = _sig("p2p_regress_workspace_bytes_for", ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_int])
 
 p2p_regress_batch = _sig("p2p_regress_batch", ctypes.c_int,
                          [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Pyramid), ctypes.POINTER(Pyramid),
@@ -123,12 +139,14 @@ p2p_absmax_batch = _sig("p2p_absmax_batch", ctypes.c_int, [ctypes.c_void_p, ctyp
 p2p_regressor_set_mode = _sig("p2p_regressor_set_mode", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int])
 p2p_regressor_get_mode = _sig("p2p_regressor_get_mode", ctypes.c_int, [ctypes.c_void_p])
 REGRESS_MODES = {"f32": 0, "fp16x2": 3, "fp16x2w": 4}
+REGRESS_GENERIC = 16          # P2P_REGRESS_GENERIC: the mode id of a handle made by p2p_regressor_create_config
+FEAT_COMB = {"pre": 0, "post": 1}
 
 EXPORTS = ["p2p_version", "p2p_last_error", "p2p_ncn_create", "p2p_ncn_destroy", "p2p_ncn_set_tile", "p2p_regressor_create",
            "p2p_regressor_destroy", "p2p_coarse_workspace_bytes", "p2p_coarse_forward", "p2p_coarse_forward_batch",
            "p2p_neigh_consensus_batch", "p2p_delta_unpack", "p2p_coarse_matches", "p2p_coarse_matches_batch", "p2p_filter_coarse_workspace_bytes", "p2p_filter_coarse_batch", "p2p_match_tail_batch", "p2p_regress", "p2p_regress_workspace_bytes", "p2p_regress_workspace_bytes_mode", "p2p_regress_batch", "p2p_regress_batch_dev", "p2p_regressor_set_mode",
            "p2p_regressor_get_mode", "p2p_conv_create", "p2p_conv_destroy", "p2p_conv_set_tile", "p2p_conv_forward", "p2p_absmax_batch", "p2p_stem_create", "p2p_stem_destroy", "p2p_stem_forward",
-           "p2p_maxpool_nhwc", "p2p_nhwc_to_nchw"]
+           "p2p_maxpool_nhwc", "p2p_nhwc_to_nchw", "p2p_regressor_create_config", "p2p_regress_workspace_bytes_for"]
 
 
 def check(status, what):

@@ -3,6 +3,7 @@
 // packers sit next to their kernels (regress.hip, regress_h2.hip, regress_wino.hip; declared in regress_common.h).  Compiled
 // as part of api.hip, not as a unit of its own.
 #include "regress_common.h"
+#include "regress_generic.hip"      // the shape-generic kernels and their handle (generic regressors; no unit of its own either)
 
 using namespace p2p;
 
@@ -102,6 +103,13 @@ static int ensure_mode(p2p_regressor *r, int mode) {
 
 extern "C" int p2p_regressor_set_mode(p2p_regressor *reg, int mode) {
     P2P_REQUIRE(reg, P2P_EINVAL, "p2p_regressor_set_mode: null handle");
+    if (reg->gen) {
+        P2P_REQUIRE(mode == P2P_REGRESS_GENERIC, P2P_EUNSUPPORTED,
+                    "p2p_regressor_set_mode: a generic regressor (p2p_regressor_create_config) runs P2P_REGRESS_GENERIC only");
+        return P2P_OK;
+    }
+    P2P_REQUIRE(mode != P2P_REGRESS_GENERIC, P2P_EUNSUPPORTED,
+                "p2p_regressor_set_mode: P2P_REGRESS_GENERIC needs a handle made by p2p_regressor_create_config");
     P2P_REQUIRE(mode_index(mode) >= 0, P2P_EINVAL, "p2p_regressor_set_mode: unknown mode %d", mode);
     // the weight stream of a mode is allocated on the HANDLE's device, whatever the caller's current device is
     int cur = 0;
@@ -178,8 +186,22 @@ extern "C" int p2p_regressor_create(const p2p_regressor_params *p, p2p_regressor
     return P2P_OK;
 }
 
+extern "C" int p2p_regressor_create_config(const p2p_regressor_config *config, const p2p_regressor_tensors *tensors,
+                                           p2p_regressor **out) {
+    GenReg *g = nullptr;
+    const int st = regressor_generic_create(config, tensors, &g);
+    if (st != P2P_OK) return st;
+    p2p_regressor *r = new p2p_regressor();      // value-initialised: no tuned stream or view
+    (void)hipGetDevice(&r->device);
+    r->mode = P2P_REGRESS_GENERIC;
+    r->gen = g;
+    *out = r;
+    return P2P_OK;
+}
+
 extern "C" void p2p_regressor_destroy(p2p_regressor *reg) {
     if (!reg) return;
+    regressor_generic_destroy(reg->gen);
     (void)hipFree(reg->dev);
     for (float *s : reg->stream)
         if (s) (void)hipFree(s);
@@ -205,6 +227,9 @@ static int regress_batch_impl(const p2p_regressor *reg1, const p2p_regressor *re
     P2P_REQUIRE(total < (1ll << 31), P2P_EINVAL, "p2p_regress: too many proposals");
     P2P_REQUIRE(proposals, P2P_EINVAL, "p2p_regress: null proposals");
     P2P_REQUIRE(reg2 ? (matches2 && probs2) : (matches1 && probs1), P2P_EINVAL, "p2p_regress: missing output buffers");
+    P2P_REQUIRE(!reg2 || !reg2->gen == !reg1->gen, P2P_EINVAL, "p2p_regress: a generic and a tuned regressor cannot be chained");
+    P2P_REQUIRE(!reg2 || !reg1->gen || memcmp(&reg1->gen->cfg, &reg2->gen->cfg, sizeof(p2p_regressor_config)) == 0, P2P_EINVAL,
+                "p2p_regress: the two generic regressors have different configurations");
     P2P_REQUIRE(!reg2 || reg2->mode == reg1->mode, P2P_EINVAL, "p2p_regress: the two regressors use different arithmetic modes");
     for (int i = 0; i < nitems; ++i) {
         const p2p_pyramid *im[2] = {im1 + i, im2 + i};
@@ -222,7 +247,8 @@ static int regress_batch_impl(const p2p_regressor *reg1, const p2p_regressor *re
         for (int b = i0; b < nitems && b < i0 + MAXB; ++b) n += counts[b];
         most = std::max(most, n);
     }
-    const size_t need = MODES[m].ws_floats((size_t)most) * sizeof(float);
+    // a generic regressor needs one unit of 8 proposals at least and cuts its chunk to what it is given
+    const size_t need = reg1->gen ? reg1->gen->per_prop * GEN_UNIT * sizeof(float) : MODES[m].ws_floats((size_t)most) * sizeof(float);
     if (need) {
         P2P_REQUIRE(workspace && ((uintptr_t)workspace & 127) == 0, P2P_EINVAL,
                     "p2p_regress: a 128-byte aligned workspace of %zu bytes (p2p_regress_workspace_bytes_mode) is needed", need);
@@ -253,15 +279,17 @@ static int regress_batch_impl(const p2p_regressor *reg1, const p2p_regressor *re
         a.is_float = is_float; a.n = n; a.nlevels = reg2 ? 2 : 1;
         a.proposals = is_float ? (const void *)((const float *)proposals + (size_t)first_prop * 4)
                                : (const void *)((const long long *)proposals + (size_t)first_prop * 4);
-        a.reg[0] = reg1->view[m];
-        a.reg[1] = reg2 ? reg2->view[m] : a.reg[0];
+        a.reg[0] = reg1->gen ? RegDev{} : reg1->view[m];
+        a.reg[1] = reg2 && !reg2->gen ? reg2->view[m] : a.reg[0];
         auto adv = [&](float *p, int cols) { return p ? p + (size_t)first_prop * cols : nullptr; };
         a.matches[0] = adv(matches1, 4); a.probs[0] = adv(probs1, 1); a.raw[0] = adv(raw1, 5);
         a.matches[1] = adv(matches2, 4); a.probs[1] = adv(probs2, 1); a.raw[1] = adv(raw2, 5);
         a.ws = (float *)workspace;      // launches of one call are ordered on the stream: they may share the scratch
         if (n > 0) {
             a.wU = nullptr; a.hinv = nullptr; a.lvl0 = 0; a.p0 = 0; a.p1 = n; a.mblocks = 0;
-            const int st = MODES[m].launch(a, n, (hipStream_t)stream);
+            const int st = reg1->gen ? launch_regress_generic(*reg1->gen, reg2 ? reg2->gen : nullptr, a, n, workspace_bytes,
+                                                              (hipStream_t)stream)
+                                     : MODES[m].launch(a, n, (hipStream_t)stream);
             if (st != P2P_OK) return st;
         }
         first_prop += n;
@@ -287,6 +315,13 @@ extern "C" size_t p2p_regress_workspace_bytes_mode(int n, int mode) {
     if (n <= 0) return 0;
     const int m = mode_index(mode);      // a mode the library does not know gets the direct mode's answer, as it always has
     return (m >= 0 ? MODES[m].ws_floats : regress_ws_base_floats)((size_t)n) * sizeof(float);
+}
+
+extern "C" size_t p2p_regress_workspace_bytes_for(const p2p_regressor *reg, int n) {
+    if (!reg || n <= 0) return 0;
+    if (!reg->gen) return p2p_regress_workspace_bytes_mode(n, reg->mode);
+    const size_t units = ((size_t)std::min(n, GEN_CAP) + GEN_UNIT - 1) / GEN_UNIT;
+    return units * GEN_UNIT * reg->gen->per_prop * sizeof(float);
 }
 
 extern "C" int p2p_regress_batch_dev(const p2p_regressor *reg1, const p2p_regressor *reg2, int nitems,

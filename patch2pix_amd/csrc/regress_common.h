@@ -413,6 +413,65 @@ constexpr size_t WW2_FLOATS = (size_t)16 * 4 * 16 * (WINO_BLK / 4);
 void pack_wino_weights(const float *conv2_w, float *ww2, int *t2);                // host
 int launch_regress_wino(const RegressArgs &a, int n, hipStream_t stream);
 
+// ---- regress_generic.hip: the shape-generic regressor (exact fp32 MFMA, one launch per layer over a chunk of proposals) ----
+// Every configuration FeatRegressNet can express within the limits of include/p2p_hip.h (p2p_regressor_config).  A call's
+// proposal slots are cut into chunks; a chunk's activations live in the caller's workspace as fp32 [sample][y][x][channel]
+// (channels innermost and padded to a multiple of 8 with zeros: an MFMA lane's K values are one 16-byte load).  A sample is
+// a proposal ('pre': image 1's channels, then image 2's) or an (image, proposal) pair ('post': sample 2 p + image).
+constexpr int GEN_MAX_LAYERS = 4;
+constexpr int GEN_UNIT = 8;              // chunks are whole units of 8 proposals
+constexpr int GEN_CAP = 256;             // proposals per chunk at most (what p2p_regress_workspace_bytes_for sizes for)
+constexpr int GEN_ROWS = 128;            // GEMM rows (sample, output pixel) of a convolution work-group: 4 waves x 32
+struct GenConv {                         // one Conv2d(padding 1, no bias) + folded BatchNorm2d
+    const float *w;                      // B fragments of v_mfma_f32_32x32x2_f32: [tap][ci / 8][ntiles][lane 64][4]
+    const float *scale, *shift;          // [co]
+    int ci, co, ker, str, hi, wi, ho, wo;        // ci: padded to a multiple of 8
+    int ntiles;                          // 32-column tiles, an even number (the last ones zero-filled past co)
+};
+struct GenFc {                           // Linear + folded BatchNorm1d + ReLU
+    const float *w;                      // B fragments of v_mfma_f32_16x16x4_f32: [k / 16][n / 16][lane 64][4]
+    const float *bias, *scale, *shift;
+    int k, n;
+};
+struct GenNet {                          // one regressor as its kernels see it
+    int n_feat, feat_idx[4], post, feat_dim, spp;      // spp: samples per proposal (1 'pre', 2 'post')
+    int n_conv, n_fc, fc_in;
+    GenConv conv[GEN_MAX_LAYERS];
+    GenFc fc[GEN_MAX_LAYERS];
+    const float *out_w, *out_b;          // final Linear [5][k_out], [5]
+    int k_out;
+};
+struct GenReg {
+    p2p_regressor_config cfg;            // normalised: entries past n_feat / n_conv / n_fc are zero
+    GenNet net;
+    float *mem;                          // one device allocation: packed weights, folds, biases
+    // workspace of a chunk of U proposals (floats per proposal): mid matches 4, V fc_in, two FC buffers fc_max each, the
+    // activation buffers a layer reads (act_a: even layers' input) and writes (act_b) -- offsets are these times U
+    size_t fc_max, act_a, act_b, per_prop;
+};
+// the parts of a chunk's workspace, in floats from its start (U proposals, a multiple of GEN_UNIT)
+static inline size_t gen_ws_mid(const GenReg &, size_t) { return 0; }
+static inline size_t gen_ws_v(const GenReg &, size_t U) { return 4 * U; }
+static inline size_t gen_ws_fc(const GenReg &g, size_t U, int which) { return (4 + g.net.fc_in + which * g.fc_max) * U; }
+static inline size_t gen_ws_act(const GenReg &g, size_t U, int which) {
+    return (4 + g.net.fc_in + 2 * g.fc_max + (which ? g.net.spp * g.act_a : 0)) * U;
+}
+int regressor_generic_create(const p2p_regressor_config *cfg, const p2p_regressor_tensors *t, GenReg **out);
+void regressor_generic_destroy(GenReg *g);
+// slots [0, n) of the launch described by `a` through reg1 (and reg2 on its un-truncated output when given), chunk by chunk
+int launch_regress_generic(const GenReg &reg1, const GenReg *reg2, const RegressArgs &a, int n, size_t workspace_bytes,
+                           hipStream_t stream);
+
+// parse_regressor_out (networks/patch2pix.py:138-155; psize 16, ptype 'center') of output o of one proposal, as the tails above
+// do it: s raw output, base the proposal coordinate the offset is relative to (un-truncated).  Returns the match coordinate
+// (o < 4) or the score (o == 4).
+__device__ __forceinline__ float regress_parse_one(float s, int o, float base, const ItemDev &I) {
+    if (o == 4) return 1.0f / (1.0f + expf(-s));
+    const float off = 16.0f * tanhf(fmaxf(s, 0.f)) - 8.0f;
+    const float hi = (float)((o == 0) ? I.W[0] : (o == 1) ? I.H[0] : (o == 2) ? I.W[1] : I.H[1]);
+    return fminf(fmaxf(base + off, 0.f), hi);
+}
+
 }  // namespace p2p
 
 // The opaque handle of include/p2p_hip.h.  A mode's kernels see the regressor through ONE RegDev: `common` (the BatchNorm / FC
@@ -420,10 +479,12 @@ int launch_regress_wino(const RegressArgs &a, int n, hipStream_t stream);
 constexpr int P2P_REGRESS_NMODES = 3;
 struct p2p_regressor {
     int device;        // the device the handle was created on: every later allocation (another mode's weight stream) goes there
-    int mode;          // P2P_REGRESS_F32 | P2P_REGRESS_FP16X2 | P2P_REGRESS_FP16X2W
+    int mode;          // P2P_REGRESS_F32 | P2P_REGRESS_FP16X2 | P2P_REGRESS_FP16X2W (tuned handles), P2P_REGRESS_GENERIC (generic ones)
     float *dev;        // BatchNorm folds + FC layers (every mode)
     float *stream[P2P_REGRESS_NMODES];      // a mode's convolution weights in its kernels' stream order (+ the BatchNorm scales with
                                             // its exponents folded in); packed on the mode's first selection, null until then
     std::vector<float> conv1_w, conv2_w, bn1s_host, bn2s_host;   // host copies the packings are built from
     p2p::RegDev common, view[P2P_REGRESS_NMODES];
+    p2p::GenReg *gen;  // a generic handle (p2p_regressor_create_config; mode P2P_REGRESS_GENERIC): everything above but `device`
+                       // and `mode` is unused; null for a tuned handle
 };

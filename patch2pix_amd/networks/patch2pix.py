@@ -41,12 +41,12 @@ def _bn_spec(prefix, n):
             f"{prefix}.num_batches_tracked": ((), "long")}
 
 
-def _regressor_spec(feat_dim):
-    spec = {"conv.0.weight": ((512, 2 * feat_dim, 3, 3), "param"), "conv.2.weight": ((512, 512, 3, 3), "param"),
-            "fc.0.weight": ((512, 512), "param"), "fc.0.bias": ((512,), "param"),
-            "fc.3.weight": ((256, 512), "param"), "fc.3.bias": ((256,), "param"),
-            "fc.6.weight": ((5, 256), "param"), "fc.6.bias": ((5,), "param")}
-    for prefix, n in (("conv.1", 512), ("conv.3", 512), ("fc.1", 512), ("fc.4", 256)):
+def _regressor_spec(layout):
+    """Keys and shapes of the reference's FeatRegressNet (networks/modules.py:76-99) for a checked configuration
+    (ops.regressor_layout)."""
+    shapes, bns = ops.regressor_shapes(layout)
+    spec = {k: (shp, "param") for k, shp in shapes.items()}
+    for prefix, n in bns.items():
         spec.update(_bn_spec(prefix, n))
     return spec
 
@@ -112,21 +112,16 @@ class Patch2Pix(nn.Module):
             rc = self.regressor_config
             self.regr_batch = config.regr_batch
             self.feat_idx = list(config.feat_idx)
-            if self.feat_idx != [0, 1, 2, 3]:
-                raise NotImplementedError(f"feat_idx {self.feat_idx}: only [0,1,2,3] is implemented")
+            # what the library implements (include/p2p_hip.h, p2p_regressor_config): NotImplementedError / ValueError otherwise
+            self._layout = ops.regressor_layout(rc, self.feat_idx)
             rc.feat_dim = sum(feat_dims[i] for i in self.feat_idx)
-            if (list(rc.conv_dims), list(rc.conv_kers), list(getattr(rc, "conv_strs", [2, 2])), list(rc.fc_dims),
-                    rc.feat_comb) != ([512, 512], [3, 3], [2, 1], [512, 256], "pre"):
-                raise NotImplementedError("only the released regressor configuration is implemented")
             self.ptype = ["center", "center"]
             self.psize = rc.psize
-            if list(self.psize) != [16, 16]:
-                raise NotImplementedError("psize must be [16,16]")
             self.pshift = rc.pshift
             self.panc = rc.panc
             self.shared = rc.shared
-            self.regress_mid = _Holder(_regressor_spec(rc.feat_dim))
-            self.regress_fine = self.regress_mid if self.shared else _Holder(_regressor_spec(rc.feat_dim))
+            self.regress_mid = _Holder(_regressor_spec(self._layout))
+            self.regress_fine = self.regress_mid if self.shared else _Holder(_regressor_spec(self._layout))
         self.to(self.device)
         self._packed = None
         self._pinned = {}        # up to 4 tickets in flight per shape
@@ -165,8 +160,9 @@ class Patch2Pix(nn.Module):
             mid = fine = None
             if self.regress_mid is not None:
                 sub = lambda p: {k[len(p):]: v for k, v in sd.items() if k.startswith(p)}
-                mid = ops.RegressorWeights(sub("regress_mid."), self.device)
-                fine = mid if self.shared else ops.RegressorWeights(sub("regress_fine."), self.device)
+                mid = ops.RegressorWeights(sub("regress_mid."), self.device, self.regressor_config, self.feat_idx)
+                fine = mid if self.shared else ops.RegressorWeights(sub("regress_fine."), self.device,
+                                                                    self.regressor_config, self.feat_idx)
             self._packed = (ncn, mid, fine)
         return self._packed
 

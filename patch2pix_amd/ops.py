@@ -160,11 +160,97 @@ def absmax_batch(x):
     return out
 
 
+FEAT_DIMS = (3, 64, 64, 128, 256)          # channels of the pyramid levels (networks/resnet.py:138-157)
+RELEASED_LAYOUT = dict(feat_idx=[0, 1, 2, 3], feat_comb="pre", conv_dims=[512, 512], conv_kers=[3, 3], conv_strs=[2, 1],
+                       fc_dims=[512, 256], psize=[16, 16])
+
+
+def regressor_layout(config=None, feat_idx=None):
+    """The regressor a checkpoint describes (`regressor_config` namespace or dict + `feat_idx`; None = the released one),
+    normalised and checked against what the library implements (include/p2p_hip.h, p2p_regressor_config): a dict
+    feat_idx / feat_comb / conv_dims / conv_kers / conv_strs / fc_dims / psize of plain lists.  A configuration the
+    reference accepts and the library does not raises NotImplementedError, a malformed one ValueError; no GPU needed."""
+    get = (lambda k, d=None: config.get(k, d)) if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
+    lay = {k: (list(v) if isinstance(v, list) else v) for k, v in RELEASED_LAYOUT.items()}
+    if feat_idx is not None:
+        lay["feat_idx"] = [int(i) for i in feat_idx]
+    if config is not None:
+        lay["feat_comb"] = get("feat_comb", "pre")
+        lay["conv_dims"] = [int(d) for d in get("conv_dims")]
+        lay["conv_kers"] = [int(k) for k in get("conv_kers")]
+        strs = get("conv_strs")                      # absent: [2] * len(conv_kers) (networks/modules.py:60)
+        lay["conv_strs"] = [int(v) for v in strs] if strs is not None else [2] * len(lay["conv_kers"])
+        lay["fc_dims"] = [int(d) for d in get("fc_dims")]
+        ps = get("psize", [16, 16])
+        lay["psize"] = [int(v) for v in ps] if isinstance(ps, (list, tuple)) else [int(ps), int(ps)]
+    fi = lay["feat_idx"]
+    if not fi or any(b <= a for a, b in zip(fi, fi[1:])) or any(i < 0 or i > 4 for i in fi):
+        raise ValueError(f"feat_idx {fi}: a non-empty, strictly ascending list of pyramid levels")
+    if 4 in fi:
+        raise NotImplementedError(f"feat_idx {fi}: level 4 is not implemented by the fine stage (the pyramid handed to the "
+                                  "library carries levels 0..3)")
+    if lay["psize"] != [16, 16]:
+        raise NotImplementedError(f"psize {lay['psize']}: psize must be [16,16]")
+    if lay["feat_comb"] not in ("pre", "post"):
+        raise ValueError(f"feat_comb {lay['feat_comb']!r}: 'pre' or 'post'")
+    nc = len(lay["conv_dims"])
+    if nc == 0 or len(lay["conv_kers"]) != nc or len(lay["conv_strs"]) != nc:
+        raise ValueError("conv_dims, conv_kers and conv_strs must be non-empty lists of one length")
+    if nc > 4 or len(lay["fc_dims"]) > 4:
+        raise NotImplementedError("at most 4 convolutions and 4 hidden FC layers are implemented")
+    for what in ("conv_dims", "fc_dims"):
+        for d in lay[what]:
+            if d <= 0:
+                raise ValueError(f"{what} {lay[what]}: dims must be positive")
+            if d % 16 or d > 1024:
+                raise NotImplementedError(f"{what} {lay[what]}: dims must be multiples of 16 in [16, 1024]")
+    side = 16
+    for k, st in zip(lay["conv_kers"], lay["conv_strs"]):
+        if k not in (1, 3, 5):
+            raise NotImplementedError(f"conv_kers {lay['conv_kers']}: kernel sizes 1, 3 and 5 are implemented")
+        if st not in (1, 2):
+            raise NotImplementedError(f"conv_strs {lay['conv_strs']}: strides 1 and 2 are implemented")
+        if side + 2 - k < 0:
+            raise ValueError(f"conv_kers {lay['conv_kers']} / conv_strs {lay['conv_strs']}: the map shrinks below 1x1")
+        side = (side + 2 - k) // st + 1
+    return lay
+
+
+def regressor_shapes(lay):
+    """State_dict keys -> shapes of the FeatRegressNet of a `regressor_layout` (weights and biases; BatchNorm vectors are
+    listed as 'conv.1' -> n, 'fc.1' -> n under 'bn'), as the reference module builds them (networks/modules.py:76-99)."""
+    feat_dim = sum(FEAT_DIMS[i] for i in lay["feat_idx"])
+    cin = feat_dim if lay["feat_comb"] == "post" else 2 * feat_dim
+    shapes, bns = {}, {}
+    for i, (d, k) in enumerate(zip(lay["conv_dims"], lay["conv_kers"])):
+        shapes[f"conv.{2 * i}.weight"] = (d, cin, k, k)
+        bns[f"conv.{2 * i + 1}"] = d
+        cin = d
+    k = lay["conv_dims"][-1] * (2 if lay["feat_comb"] == "post" else 1)
+    for i, d in enumerate(lay["fc_dims"]):
+        shapes[f"fc.{3 * i}.weight"], shapes[f"fc.{3 * i}.bias"] = (d, k), (d,)
+        bns[f"fc.{3 * i + 1}"] = d
+        k = d
+    n = 3 * len(lay["fc_dims"])
+    shapes[f"fc.{n}.weight"], shapes[f"fc.{n}.bias"] = (5, k), (5,)
+    return shapes, bns
+
+
 class RegressorWeights:
     """Device-resident packed FeatRegressNet (reference networks/modules.py:56-112).
-    `sd` maps the sub-state_dict keys ('conv.0.weight', 'fc.6.bias', ...) to tensors."""
+    `sd` maps the sub-state_dict keys ('conv.0.weight', 'fc.6.bias', ...) to tensors.  `config` / `feat_idx`: the
+    checkpoint's `regressor_config` / `feat_idx` (None = the released ones).  The released configuration runs the tuned
+    kernels; every other one -- or `generic=True` -- a generic handle (p2p_regressor_create_config: exact fp32 MFMA, one
+    launch per layer)."""
 
-    def __init__(self, sd, device):
+    def __init__(self, sd, device, config=None, feat_idx=None, generic=False):
+        lay = regressor_layout(config, feat_idx)
+        self.layout = lay
+        self.generic = bool(generic) or lay != RELEASED_LAYOUT
+        self.device = torch.device(device)
+        if self.generic:
+            self._create_generic(sd, lay)
+            return
         exp = {"conv.0.weight": (512, 518, 3, 3), "conv.2.weight": (512, 512, 3, 3), "fc.0.weight": (512, 512),
                "fc.3.weight": (256, 512), "fc.6.weight": (5, 256)}
         for k, shp in exp.items():
@@ -186,16 +272,51 @@ class RegressorWeights:
         self.handle = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.p2p_regressor_create(ctypes.byref(p), ctypes.byref(self.handle)), "p2p_regressor_create")
-        self.device = torch.device(device)
         env = os.environ.get("P2P_REGRESS_MODE")       # tools: the mode new handles start in (read here, not in the library)
         if env:
             self.set_mode(env)
+
+    def _create_generic(self, sd, lay):
+        shapes, bns = regressor_shapes(lay)
+        for k, shp in shapes.items():
+            if k not in sd or tuple(sd[k].shape) != shp:
+                got = tuple(sd[k].shape) if k in sd else "no tensor"
+                raise ValueError(f"regressor {k}: the configuration asks for shape {shp}, the state_dict has {got}")
+        keep = {k: _host(v) for k, v in sd.items() if v.is_floating_point()}
+
+        def bn(prefix):
+            return _lib.BnParams(keep[prefix + ".weight"].data_ptr(), keep[prefix + ".bias"].data_ptr(),
+                                 keep[prefix + ".running_mean"].data_ptr(), keep[prefix + ".running_var"].data_ptr())
+
+        c, t = _lib.RegressorConfig(), _lib.RegressorTensors()
+        c.n_feat = len(lay["feat_idx"])
+        for i, j in enumerate(lay["feat_idx"]):
+            c.feat_idx[i] = j
+        c.feat_comb = _lib.FEAT_COMB[lay["feat_comb"]]
+        c.n_conv, c.n_fc, c.psize = len(lay["conv_dims"]), len(lay["fc_dims"]), lay["psize"][0]
+        for i in range(c.n_conv):
+            c.conv_dim[i], c.conv_ker[i], c.conv_str[i] = lay["conv_dims"][i], lay["conv_kers"][i], lay["conv_strs"][i]
+            t.conv_w[i] = keep[f"conv.{2 * i}.weight"].data_ptr()
+            t.conv_bn[i] = bn(f"conv.{2 * i + 1}")
+        for i in range(c.n_fc):
+            c.fc_dim[i] = lay["fc_dims"][i]
+            t.fc_w[i], t.fc_b[i] = keep[f"fc.{3 * i}.weight"].data_ptr(), keep[f"fc.{3 * i}.bias"].data_ptr()
+            t.fc_bn[i] = bn(f"fc.{3 * i + 1}")
+        t.out_w, t.out_b = keep[f"fc.{3 * c.n_fc}.weight"].data_ptr(), keep[f"fc.{3 * c.n_fc}.bias"].data_ptr()
+        self.handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.p2p_regressor_create_config(ctypes.byref(c), ctypes.byref(t), ctypes.byref(self.handle)),
+                       "p2p_regressor_create_config")
 
     def set_mode(self, mode):
         """'fp16x2w' (default: fp32-equivalent, two fp16 planes under exact power-of-two scales, 3 MFMA products, the second
         convolution as Winograd F(2x2,3x3) GEMMs), 'fp16x2' (the same arithmetic, both convolutions direct, one launch) or 'f32'
         (exact fp32 MFMA).  The first selection of a
         non-default mode packs and uploads that mode's weight stream (host work, ~1 s)."""
+        if self.generic:
+            if mode == "generic":
+                return
+            raise NotImplementedError(f"regressor mode {mode!r}: a generic regressor runs the exact-fp32 generic kernels only")
         if mode not in _lib.REGRESS_MODES:
             removed = {"bf16x2": "round 5", "bf16x3": "round 4"}
             why = f" ({mode!r} was removed in {removed[mode]})" if mode in removed else ""
@@ -207,7 +328,7 @@ class RegressorWeights:
     @property
     def mode(self):
         code = _lib.p2p_regressor_get_mode(self.handle)
-        return {v: k for k, v in _lib.REGRESS_MODES.items()}[code]
+        return "generic" if code == _lib.REGRESS_GENERIC else {v: k for k, v in _lib.REGRESS_MODES.items()}[code]
 
     def __del__(self):
         if getattr(self, "handle", None) and _lib is not None:
@@ -421,9 +542,10 @@ def match_tail_batch(fine, scores, coarse, counts, scale, io_thres):
     return out_m, out_s, out_c, out_n
 
 
-def regress_batch_dev(reg1, reg2, pyrs1, pyrs2, proposals, counts, want_raw=False):
+def regress_batch_dev(reg1, reg2, pyrs1, pyrs2, proposals, counts, want_raw=False, out=None):
     """regress_batch with the proposal counts in device memory: proposals [B,stride,4] (int64 or float32), counts int32
-    [B] on the GPU; every output is padded to [B,stride,...], rows beyond counts[b] are left uninitialised."""
+    [B] on the GPU; every output is padded to [B,stride,...], rows beyond counts[b] are left uninitialised -- or, with
+    `out` (a dict of contiguous float32 buffers of those shapes by output name), as the caller filled them."""
     nb, stride, _ = proposals.shape
     dev = proposals.device
     if proposals.dtype not in (torch.int64, torch.float32):
@@ -437,6 +559,7 @@ def regress_batch_dev(reg1, reg2, pyrs1, pyrs2, proposals, counts, want_raw=Fals
         pb, kb = _pyramid(pyrs2[i])
         pyr_a[i], pyr_b[i] = pa, pb
         keep.append((ka, kb))
+    given = out or {}
     two = reg2 is not None
     out = {"matches1": torch.empty((nb, stride, 4), device=dev), "probs1": torch.empty((nb, stride), device=dev)}
     if two:
@@ -445,6 +568,11 @@ def regress_batch_dev(reg1, reg2, pyrs1, pyrs2, proposals, counts, want_raw=Fals
         out["raw1"] = torch.empty((nb, stride, 5), device=dev)
         if two:
             out["raw2"] = torch.empty((nb, stride, 5), device=dev)
+    for k in out:
+        if k in given:
+            if given[k].shape != out[k].shape or given[k].dtype != torch.float32 or not given[k].is_contiguous() or given[k].device != dev:
+                raise ValueError(f"out[{k!r}] must be a contiguous float32 tensor of shape {tuple(out[k].shape)} on {dev}")
+            out[k] = given[k]
     g = lambda k: out[k].data_ptr() if k in out else None
     if nb and stride:
         with torch.cuda.device(dev):
@@ -458,6 +586,11 @@ def regress_batch_dev(reg1, reg2, pyrs1, pyrs2, proposals, counts, want_raw=Fals
     return out
 
 
+# Tests and tools: a cap (bytes) on the scratch handed to a GENERIC regressor, which cuts its chunks to what it is given
+# (at least p2p_regress_workspace_bytes_for(handle, 8); results do not depend on it).
+generic_scratch_limit = None
+
+
 def _regress_scratch(dev, n, reg=None):
     """Scratch of one regress call (the pooled convolution features wait there for the batched FC tail; in the default mode
     also the Winograd-transformed input of the second convolution, chunk by chunk): a fresh stream-ordered allocation per
@@ -465,7 +598,9 @@ def _regress_scratch(dev, n, reg=None):
     if reg is None:
         nbytes = _lib.p2p_regress_workspace_bytes(int(n))
     else:
-        nbytes = _lib.p2p_regress_workspace_bytes_mode(int(n), _lib.p2p_regressor_get_mode(reg.handle))
+        nbytes = _lib.p2p_regress_workspace_bytes_for(reg.handle, int(n))
+        if generic_scratch_limit is not None and getattr(reg, "generic", False):
+            nbytes = min(nbytes, int(generic_scratch_limit))
     return torch.empty(max(int(nbytes), 128), dtype=torch.uint8, device=dev)
 
 

@@ -15,10 +15,22 @@ from argparse import Namespace
 import torch
 
 
-def default_regressor_config():
-    """Defaults of train_patch2pix.py:46-54 as stored in a checkpoint ('regressor_config')."""
-    return Namespace(conv_dims=[512, 512], conv_kers=[3, 3], conv_strs=[2, 1], fc_dims=[512, 256],
-                     feat_comb="pre", psize=[16, 16], pshift=8, panc=1, shared=False)
+def default_regressor_config(**overrides):
+    """Defaults of train_patch2pix.py:46-54 as stored in a checkpoint ('regressor_config'); `overrides` replace fields
+    (conv_strs=None drops the field, as checkpoints of older training runs do: networks/modules.py:60)."""
+    cfg = dict(conv_dims=[512, 512], conv_kers=[3, 3], conv_strs=[2, 1], fc_dims=[512, 256],
+               feat_comb="pre", psize=[16, 16], pshift=8, panc=1, shared=False)
+    cfg.update(overrides)
+    if cfg["conv_strs"] is None:
+        del cfg["conv_strs"]
+    return Namespace(**cfg)
+
+
+_FEAT_DIMS = (3, 64, 64, 128, 256)
+
+
+def _conv_strs(rc):
+    return list(getattr(rc, "conv_strs", None) or [2] * len(rc.conv_kers))
 
 
 def _xavier(gen, *shape):
@@ -81,45 +93,55 @@ def _ncn(gen, sd, peaky):
     sd["ncn.conv.2.bias"] = 0.01 * torch.randn(1, generator=gen)
 
 
-def _regressor(gen, sd, prefix, feat_dim=259):
-    sd[prefix + ".conv.0.weight"] = _xavier(gen, 512, 2 * feat_dim, 3, 3)
-    _bn(gen, sd, prefix + ".conv.1", 512)
-    sd[prefix + ".conv.2.weight"] = _xavier(gen, 512, 512, 3, 3)
-    _bn(gen, sd, prefix + ".conv.3", 512)
-    sd[prefix + ".fc.0.weight"] = _xavier(gen, 512, 512)
-    sd[prefix + ".fc.0.bias"] = 0.05 * torch.randn(512, generator=gen)
-    _bn(gen, sd, prefix + ".fc.1", 512)
-    sd[prefix + ".fc.3.weight"] = _xavier(gen, 256, 512)
-    sd[prefix + ".fc.3.bias"] = 0.05 * torch.randn(256, generator=gen)
-    _bn(gen, sd, prefix + ".fc.4", 256)
-    sd[prefix + ".fc.6.weight"] = 8.0 * _xavier(gen, 5, 256)
+def _regressor(gen, sd, prefix, feat_dim=259, regressor_config=None):
+    """One FeatRegressNet (networks/modules.py:56-112) of `regressor_config` (None: the released one) on `feat_dim`
+    channels per image.  The draws of the released configuration come in the order they always had."""
+    rc = regressor_config or default_regressor_config()
+    post = rc.feat_comb == "post"
+    cin = feat_dim if post else 2 * feat_dim
+    for i, (d, k) in enumerate(zip(rc.conv_dims, rc.conv_kers)):
+        sd[f"{prefix}.conv.{2 * i}.weight"] = _xavier(gen, d, cin, k, k)
+        _bn(gen, sd, f"{prefix}.conv.{2 * i + 1}", d)
+        cin = d
+    k = rc.conv_dims[-1] * (2 if post else 1)
+    for i, d in enumerate(rc.fc_dims):
+        sd[f"{prefix}.fc.{3 * i}.weight"] = _xavier(gen, d, k)
+        sd[f"{prefix}.fc.{3 * i}.bias"] = 0.05 * torch.randn(d, generator=gen)
+        _bn(gen, sd, f"{prefix}.fc.{3 * i + 1}", d)
+        k = d
+    last = f"{prefix}.fc.{3 * len(rc.fc_dims)}"
+    sd[last + ".weight"] = 8.0 * _xavier(gen, 5, k)
     # Centre the five outputs in the sensitive range of 16*tanh(relu(.)) / sigmoid(.): with random
     # features the pooled activations barely vary between proposals, so an un-calibrated bias
     # saturates tanh and makes every proposal regress to the same corner.
     target = torch.tensor([0.45, 0.5, 0.55, 0.4, 0.2]) + 0.05 * torch.randn(5, generator=gen)
-    sd[prefix + ".fc.6.bias"] = torch.zeros(5)
-    sd[prefix + ".fc.6.bias"] = target - _pilot_outputs(gen, sd, prefix, feat_dim).mean(dim=0)
+    sd[last + ".bias"] = torch.zeros(5)
+    sd[last + ".bias"] = target - _pilot_outputs(gen, sd, prefix, feat_dim, regressor_config=rc).mean(dim=0)
 
 
-def _pilot_outputs(gen, sd, prefix, feat_dim, n=6):
+def _pilot_outputs(gen, sd, prefix, feat_dim, n=6, regressor_config=None):
     """Raw regressor outputs on a few random unit-norm patches (plain torch; calibration only)."""
     import torch.nn.functional as F
+    rc = regressor_config or default_regressor_config()
 
     def bn(x, name, shape):
         g = lambda k: sd[f"{prefix}.{name}.{k}"].view(shape)
         return (x - g("running_mean")) / torch.sqrt(g("running_var") + 1e-5) * g("weight") + g("bias")
 
+    def conv(u):
+        for i, st in enumerate(_conv_strs(rc)):
+            u = bn(F.conv2d(u, sd[f"{prefix}.conv.{2 * i}.weight"], stride=st, padding=1), f"conv.{2 * i + 1}", (1, -1, 1, 1))
+        return torch.relu(u).amax(dim=(2, 3))
+
     halves = []
     for _ in range(2):
         t = torch.relu(torch.randn(n, feat_dim, 16, 16, generator=gen) + 0.3)
         halves.append(t / (t.pow(2).sum(dim=1, keepdim=True) + 1e-6).sqrt())
-    z = torch.cat(halves, dim=1)
-    u = bn(F.conv2d(z, sd[prefix + ".conv.0.weight"], stride=2, padding=1), "conv.1", (1, -1, 1, 1))
-    u = bn(F.conv2d(u, sd[prefix + ".conv.2.weight"], padding=1), "conv.3", (1, -1, 1, 1))
-    v = torch.relu(u).amax(dim=(2, 3))
-    v = torch.relu(bn(F.linear(v, sd[prefix + ".fc.0.weight"], sd[prefix + ".fc.0.bias"]), "fc.1", (1, -1)))
-    v = torch.relu(bn(F.linear(v, sd[prefix + ".fc.3.weight"], sd[prefix + ".fc.3.bias"]), "fc.4", (1, -1)))
-    return F.linear(v, sd[prefix + ".fc.6.weight"], sd[prefix + ".fc.6.bias"])
+    v = torch.cat([conv(h) for h in halves], dim=1) if rc.feat_comb == "post" else conv(torch.cat(halves, dim=1))
+    for i in range(len(rc.fc_dims)):
+        v = torch.relu(bn(F.linear(v, sd[f"{prefix}.fc.{3 * i}.weight"], sd[f"{prefix}.fc.{3 * i}.bias"]), f"fc.{3 * i + 1}", (1, -1)))
+    last = f"{prefix}.fc.{3 * len(rc.fc_dims)}"
+    return F.linear(v, sd[last + ".weight"], sd[last + ".bias"])
 
 
 def contrast_shift(sd, kappa=4.0, images=2, height=240, width=320):
@@ -154,9 +176,11 @@ def contrast_shift(sd, kappa=4.0, images=2, height=240, width=320):
     return torch.round((z.mean(dim=1) + kappa * z.std(dim=1)) * 64) / 64
 
 
-def make_state_dict(seed=0, peaky_ncn=True, backbone=True, contrast=None):
+def make_state_dict(seed=0, peaky_ncn=True, backbone=True, contrast=None, regressor_config=None, feat_idx=None):
     """Reference-layout state_dict (fp32 CPU tensors) from one integer seed.  `contrast`: None (plain backbone), a
-    float kappa (calibrate `contrast_shift` here) or the [256] shift tensor of a fixture."""
+    float kappa (calibrate `contrast_shift` here) or the [256] shift tensor of a fixture.  `regressor_config` / `feat_idx`:
+    the regressors of another configuration than the released one (shared=True: one regressor, stored under both names
+    like the reference's state_dict of a model whose regress_fine IS regress_mid)."""
     gen = torch.Generator().manual_seed(int(seed))
     sd = {}
     if backbone:
@@ -165,15 +189,23 @@ def make_state_dict(seed=0, peaky_ncn=True, backbone=True, contrast=None):
             shift = contrast_shift(sd, float(contrast)) if isinstance(contrast, (int, float)) else torch.as_tensor(contrast).float()
             sd["extract.layer3.5.bn2.bias"] = sd["extract.layer3.5.bn2.bias"] - shift
     _ncn(gen, sd, peaky_ncn)
-    _regressor(gen, sd, "regress_mid")
-    _regressor(gen, sd, "regress_fine")
+    feat_dim = sum(_FEAT_DIMS[i] for i in (feat_idx if feat_idx is not None else (0, 1, 2, 3)))
+    _regressor(gen, sd, "regress_mid", feat_dim, regressor_config)
+    if regressor_config is not None and getattr(regressor_config, "shared", False):
+        sd.update({"regress_fine." + k[len("regress_mid."):]: v for k, v in list(sd.items()) if k.startswith("regress_mid.")})
+    else:
+        _regressor(gen, sd, "regress_fine", feat_dim, regressor_config)
     return sd
 
 
-def make_checkpoint(seed=0, **kw):
+def make_checkpoint(seed=0, regressor_config=None, feat_idx=None, **kw):
     """A dict with the reference checkpoint schema (utils/train/helper.py:10-20)."""
-    return {"last_epoch": 0, "best_vals": None, "backbone": "ResNet34", "feat_idx": [0, 1, 2, 3],
-            "change_stride": True, "regressor_config": default_regressor_config(),
+    rc = regressor_config if regressor_config is not None else default_regressor_config()
+    fi = list(feat_idx) if feat_idx is not None else [0, 1, 2, 3]
+    if regressor_config is not None or feat_idx is not None:
+        kw = dict(kw, regressor_config=rc, feat_idx=fi)
+    return {"last_epoch": 0, "best_vals": None, "backbone": "ResNet34", "feat_idx": fi,
+            "change_stride": True, "regressor_config": rc,
             "state_dict": make_state_dict(seed, **kw), "optim": None}
 
 
