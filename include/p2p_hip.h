@@ -202,6 +202,25 @@ int p2p_coarse_matches_batch(const float *corr4d, const uint8_t *delta, int batc
                              int ksize, int upsample, int center, int64_t *matches_out, float *scores_out,
                              p2p_stream_t stream);
 
+/* The topk best candidates per cell and direction, and raw scores (since version 105) -- reference
+ * ncn/extract_ncmatches.py:96-158 (corr_to_matches_topk) in both directions, concatenated B->A first then A->B the way
+ * cal_coarse_matches concatenates corr_to_matches; do_softmax = 0 is the `do_softmax=False` of both extractors (:30, :45,
+ * :111, :126): the score is the consensus value itself, bit for bit.  With nA = hA'*wA', nB = hB'*wB' per pair:
+ *   matches_out [B, topk*(nB+nA), 4] int64, scores_out [B, topk*(nB+nA)] fp32
+ *   row t*nB + c             rank t of B cell c among the A cells     (the reference's view(batch, topk, -1))
+ *   row topk*nB + r*topk + t rank t of A cell r among the B cells     (view(batch, -1, topk))
+ * Order within a column / row: descending value; equal values by ascending flat cell index.  torch.topk leaves ties
+ * unspecified, so this is the library's definition; it extends the "first index attaining the maximum" of the two
+ * functions above.  Only values above -inf are candidates (NaN compares false and is none either): a column / row with
+ * fewer than topk of them repeats, from the first missing rank on, one clamped cell (the last of the other image) with
+ * score -inf (do_softmax = 0) or 0 (do_softmax = 1; NaN if no value is above -inf).  Softmax scores are expf(x_t - max) / sum expf(x - max) with the sum taken exactly as those functions
+ * take it: topk = 1 with do_softmax = 1 gives their matches and scores bit for bit.
+ * 1 <= topk <= 8 and topk <= min(nA, nB) (torch.topk raises beyond that as well), else P2P_EINVAL; every other argument as
+ * in the batch form above.  One pass over the volume per rank (csrc/coarse.hip, section 5).                        */
+int p2p_coarse_matches_topk_batch(const float *corr4d, const uint8_t *delta, int batch, int hA, int wA, int hB, int wB,
+                                  int ksize, int upsample, int center, int topk, int do_softmax,
+                                  int64_t *matches_out, float *scores_out, p2p_stream_t stream);
+
 /* filter_coarse -- reference networks/utils.py:38-72 without the `ptmax` sampling (which draws from the host's numpy
  * RNG and therefore stays on the host): per batch item the lexicographically sorted distinct rows of matches [n,4]
  * with the score of their first occurrence; `mutual` keeps rows that occur more than once; an empty selection leaves

@@ -537,7 +537,7 @@ static void launch_mm_apply(const float *X, int nA, int nB, const int *rkey, con
 //    volume and batch size
 // ------------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------------
-// 5. matches (ncn/extract_ncmatches.py:6-94 twice; patch2pix.py:340-375)
+// 5. matches (ncn/extract_ncmatches.py:6-94 twice; patch2pix.py:340-375) and their top-k form (:96-158)
 // ------------------------------------------------------------------------------------------------
 struct MatchArgs {
     const float *X;
@@ -555,7 +555,10 @@ __device__ __forceinline__ MatchArgs match_args_of_pair(MatchArgs m, size_t z) {
     return m;
 }
 
-__device__ __forceinline__ void emit_match(const MatchArgs &m, int out_row, int ra, int cb, float sum_exp) {
+// one match row: cell (ra, cb) relocalised and scaled to pixels; `s` is the softmax denominator of the row's maximum
+// (RECIP) or the score itself (the top-k kernels)
+template <bool RECIP>
+__device__ __forceinline__ void emit_match_as(const MatchArgs &m, int out_row, int ra, int cb, float s) {
     int ia = ra / m.wA, ja = ra - ia * m.wA, ib = cb / m.wB, jb = cb - ib * m.wB;
     if (m.ksize > 1 && m.delta) {
         const int k = m.ksize;
@@ -570,7 +573,10 @@ __device__ __forceinline__ void emit_match(const MatchArgs &m, int out_row, int 
     const long long up = m.upsample, off = m.center ? m.upsample / 2 : 0;
     long long *o = m.matches + (size_t)out_row * 4;
     o[0] = up * ja + off; o[1] = up * ia + off; o[2] = up * jb + off; o[3] = up * ib + off;
-    m.scores[out_row] = 1.0f / sum_exp;       // max of softmax = exp(0) / sum exp(x - max)
+    m.scores[out_row] = RECIP ? 1.0f / s : s;       // max of softmax = exp(0) / sum exp(x - max)
+}
+__device__ __forceinline__ void emit_match(const MatchArgs &m, int out_row, int ra, int cb, float sum_exp) {
+    emit_match_as<true>(m, out_row, ra, cb, sum_exp);
 }
 
 // direction B->A: one block per 16 columns (a row of the block = half a 128-byte line: 8-column blocks fetched every line of
@@ -640,6 +646,108 @@ __global__ __launch_bounds__(256) void match_rows_kernel(MatchArgs m_) {
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) sum += __shfl_xor(sum, s);
     if (lane == 0) emit_match(m, nB + row, row, arg, sum);
+}
+
+// The topk best cells per cell and direction (corr_to_matches_topk, extract_ncmatches.py:96-158), ordered by descending
+// value and, among equal values, ascending index.  No candidate list is kept (indexed at run time it would live in
+// scratch): rank t is the arg-max over the cells that come strictly AFTER rank t-1's (value, index) in that order, found
+// by one more pass of the reduction of the kernels above over a volume that sits in L2 / Infinity Cache.  topk passes, plus
+// the softmax sum after rank 0 -- the same slices and the same tree as above, so rank 0 of topk = 1 is their output bit for
+// bit.  do_softmax = 0: the score is the value itself.
+__device__ __forceinline__ bool topk_after(float v, int i, float pv, int pi) { return v < pv || (v == pv && i > pi); }
+
+// direction B->A, rank t of column c -> row t*nB + c (the reference's view(batch, topk, -1))
+__global__ __launch_bounds__(256) void match_cols_topk_kernel(MatchArgs m_, int topk, int do_softmax) {
+    const MatchArgs m = match_args_of_pair(m_, blockIdx.z);
+    __shared__ float smax[MC_SLICES][MC_COLS];
+    __shared__ int sarg[MC_SLICES][MC_COLS];
+    __shared__ float ssum[MC_SLICES][MC_COLS];
+    const int nA = m.hA * m.wA, nB = m.hB * m.wB;
+    const int cs = threadIdx.x & (MC_COLS - 1), rs = threadIdx.x / MC_COLS;
+    const int col = blockIdx.x * MC_COLS + cs;
+    const bool ok = col < nB;
+    float pv = INFINITY, top = 0.f, total = 1.f;     // previous rank's value (everything comes after +inf, -1), rank 0's, sum exp
+    int pi = -1;
+    for (int t = 0; t < topk; ++t) {
+        float best = -INFINITY;
+        int arg = 0x7fffffff;
+        if (ok)
+            for (int r = rs; r < nA; r += MC_SLICES) {
+                const float v = m.X[(size_t)r * nB + col];
+                if (topk_after(v, r, pv, pi) && v > best) { best = v; arg = r; }
+            }
+        smax[rs][cs] = best; sarg[rs][cs] = arg;
+        __syncthreads();
+        float gb = smax[0][cs];
+        int ga = sarg[0][cs];
+#pragma unroll
+        for (int s = 1; s < MC_SLICES; ++s) {
+            const float v = smax[s][cs];
+            const int a = sarg[s][cs];
+            if (v > gb || (v == gb && a < ga)) { gb = v; ga = a; }
+        }
+        if (t == 0) {
+            top = gb;
+            if (do_softmax) {
+                float sum = 0.f;
+                if (ok)
+                    for (int r = rs; r < nA; r += MC_SLICES) sum += expf(m.X[(size_t)r * nB + col] - gb);
+                ssum[rs][cs] = sum;
+                __syncthreads();
+                if (rs == 0) {
+                    total = 0.f;
+#pragma unroll
+                    for (int s = 0; s < MC_SLICES; ++s) total += ssum[s][cs];
+                }
+            }
+        }
+        // topk <= nA finite values always leave a candidate; a volume of NaN / -inf does not, and must not index past the delta
+        ga = min(ga, nA - 1);
+        if (rs == 0 && ok)
+            emit_match_as<false>(m, t * nB + col, ga, col, do_softmax ? (t == 0 ? 1.0f : expf(gb - top)) / total : gb);
+        pv = gb; pi = ga;
+        __syncthreads();        // the next rank overwrites smax / sarg
+    }
+}
+
+// direction A->B, rank t of row r -> row topk*nB + r*topk + t (view(batch, -1, topk), after the whole B->A list): one wave per row
+__global__ __launch_bounds__(256) void match_rows_topk_kernel(MatchArgs m_, int topk, int do_softmax) {
+    const MatchArgs m = match_args_of_pair(m_, blockIdx.z);
+    const int nA = m.hA * m.wA, nB = m.hB * m.wB;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= nA) return;
+    const float *x = m.X + (size_t)row * nB;
+    float pv = INFINITY, top = 0.f, total = 1.f;
+    int pi = -1;
+    for (int t = 0; t < topk; ++t) {
+        float best = -INFINITY;
+        int arg = 0x7fffffff;
+        for (int c = lane; c < nB; c += 64) {
+            const float v = x[c];
+            if (topk_after(v, c, pv, pi) && v > best) { best = v; arg = c; }
+        }
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) {
+            const float ov = __shfl_xor(best, s);
+            const int oa = __shfl_xor(arg, s);
+            if (ov > best || (ov == best && oa < arg)) { best = ov; arg = oa; }
+        }
+        if (t == 0) {
+            top = best;
+            if (do_softmax) {
+                float sum = 0.f;
+                for (int c = lane; c < nB; c += 64) sum += expf(x[c] - best);
+#pragma unroll
+                for (int s = 32; s >= 1; s >>= 1) sum += __shfl_xor(sum, s);
+                total = sum;
+            }
+        }
+        arg = min(arg, nB - 1);
+        if (lane == 0)
+            emit_match_as<false>(m, topk * nB + row * topk + t, row, arg, do_softmax ? (t == 0 ? 1.0f : expf(best - top)) / total : best);
+        pv = best; pi = arg;
+    }
 }
 
 __global__ void delta_unpack_kernel(const uint8_t *__restrict__ delta, size_t n, int k, long long *__restrict__ out) {
@@ -856,6 +964,25 @@ extern "C" int p2p_coarse_matches_batch(const float *corr4d, const uint8_t *delt
     hipLaunchKernelGGL(match_cols_kernel, dim3(ceil_div(nB, MC_COLS), 1, batch), dim3(256), 0, (hipStream_t)stream, m);
     hipLaunchKernelGGL(match_rows_kernel, dim3(ceil_div(nA, 4), 1, batch), dim3(256), 0, (hipStream_t)stream, m);
     return check_launch("match kernels");
+}
+
+extern "C" int p2p_coarse_matches_topk_batch(const float *corr4d, const uint8_t *delta, int batch, int hA, int wA, int hB, int wB,
+                                             int ksize, int upsample, int center, int topk, int do_softmax,
+                                             int64_t *matches_out, float *scores_out, p2p_stream_t stream) {
+    P2P_REQUIRE(corr4d && matches_out && scores_out, P2P_EINVAL, "p2p_coarse_matches_topk: null argument");
+    P2P_REQUIRE(batch >= 1 && batch <= 65535, P2P_EINVAL, "p2p_coarse_matches_topk: batch %d out of range", batch);
+    P2P_REQUIRE(hA > 0 && wA > 0 && hB > 0 && wB > 0 && ksize >= 1, P2P_EINVAL, "p2p_coarse_matches_topk: bad sizes");
+    P2P_REQUIRE(ksize == 1 || delta, P2P_EINVAL, "p2p_coarse_matches_topk: delta required when ksize > 1");
+    const int nA = hA * wA, nB = hB * wB;
+    P2P_REQUIRE(topk >= 1 && topk <= 8, P2P_EINVAL, "p2p_coarse_matches_topk: topk %d out of range (1 to 8)", topk);
+    P2P_REQUIRE(topk <= std::min(nA, nB), P2P_EINVAL, "p2p_coarse_matches_topk: topk %d exceeds the %d cells of an image", topk,
+                std::min(nA, nB));
+    MatchArgs m{corr4d, delta, hA, wA, hB, wB, ksize, upsample, center, (long long *)matches_out, scores_out,
+                (size_t)nA * nB, (size_t)topk * ((size_t)nA + nB)};
+    const int sm = do_softmax ? 1 : 0;
+    hipLaunchKernelGGL(match_cols_topk_kernel, dim3(ceil_div(nB, MC_COLS), 1, batch), dim3(256), 0, (hipStream_t)stream, m, topk, sm);
+    hipLaunchKernelGGL(match_rows_topk_kernel, dim3(ceil_div(nA, 4), 1, batch), dim3(256), 0, (hipStream_t)stream, m, topk, sm);
+    return check_launch("top-k match kernels");
 }
 
 extern "C" int p2p_coarse_matches(const float *corr4d, const uint8_t *delta, int hA, int wA, int hB, int wB, int ksize,

@@ -188,22 +188,32 @@ class Patch2Pix(nn.Module):
             return corr4d, delta4d, feat1s, feat2s
         return corr4d, delta4d
 
-    def cal_coarse_matches(self, corr4d, delta4d, ksize=1, do_softmax=True, upsample=16, sort=False,
-                           center=True, pshift=0):
-        if not do_softmax:
-            raise NotImplementedError("cal_coarse_matches(do_softmax=False) is not implemented")
+    def _packed_delta(self, delta4d, ksize):
         if delta4d is not None and not isinstance(delta4d, Delta4d):
             di, dj, dk, dl = delta4d            # reference-format int64 planes -> packed byte
             s = ((di * ksize + dj) * ksize + dk) * ksize + dl
             delta4d = Delta4d(s[:, 0].to(torch.uint8).contiguous(), ksize)
-        nb, _, h1, w1, h2, w2 = corr4d.shape
-        matches_, score_ = ops.coarse_matches_batch(corr4d[:, 0], delta4d.packed if delta4d is not None else None,
-                                                    ksize, upsample, center)
+        return delta4d.packed if delta4d is not None else None
+
+    def cal_coarse_matches(self, corr4d, delta4d, ksize=1, do_softmax=True, upsample=16, sort=False,
+                           center=True, pshift=0):
+        packed = self._packed_delta(delta4d, ksize)
+        if do_softmax:
+            matches_, score_ = ops.coarse_matches_batch(corr4d[:, 0], packed, ksize, upsample, center)
+        else:       # raw consensus values as scores: the top-k entry with one candidate per cell
+            matches_, score_ = ops.coarse_matches_topk_batch(corr4d[:, 0], packed, ksize, upsample, center, 1, False)
         if sort:
             order = torch.sort(-score_)[1]
             score_ = torch.gather(score_, 1, order)
             matches_ = torch.gather(matches_, 1, order.unsqueeze(-1).expand(-1, -1, 4))
         return matches_, score_
+
+    def cal_coarse_matches_topk(self, corr4d, delta4d, topk, ksize=1, do_softmax=True, upsample=16, center=True):
+        """cal_coarse_matches with the `topk` best candidates per cell and direction (corr_to_matches_topk,
+        ncn/extract_ncmatches.py:96-158, in both directions): ([B,topk*(nB+nA),4] int64, [B,topk*(nB+nA)] fp32); rank t of
+        B cell c in row t*nB + c, rank t of A cell r in row topk*nB + r*topk + t; ties by ascending cell index."""
+        return ops.coarse_matches_topk_batch(corr4d[:, 0], self._packed_delta(delta4d, ksize), ksize, upsample, center,
+                                             topk, do_softmax)
 
     def shift_to_anchors(self, matches):
         """patch2pix.py:377-402: panc == 8 replaces each match by its 8 corner-shifted anchors."""
@@ -248,6 +258,27 @@ class Patch2Pix(nn.Module):
         coarse_matches, match_scores = self.cal_coarse_matches(corr4d, delta4d, ksize=ksize,
                                                                upsample=self.upsample, center=center)
         return filter_coarse(coarse_matches, match_scores, ncn_thres, mutual)
+
+    def predict_coarse_topk(self, im1, im2, topk, ksize=2, ncn_thres=0.0, mutual=False, center=True):
+        """predict_coarse over `topk` candidates per cell and direction."""
+        corr4d, delta4d = self.forward(im1, im2, ksize)
+        coarse_matches, match_scores = self.cal_coarse_matches_topk(corr4d, delta4d, topk, ksize=ksize,
+                                                                    upsample=self.upsample, center=center)
+        return filter_coarse(coarse_matches, match_scores, ncn_thres, mutual)
+
+    def predict_fine_topk(self, im1, im2, topk, ksize=2, ncn_thres=0.0, mutual=True, return_all=False):
+        """predict_fine over `topk` candidates per cell and direction: k times the proposals from one coarse stage, each
+        scored by the regressors (host-side filter_coarse; same return layout as predict_fine)."""
+        feats1, feats2 = self._pyramids(im1, im2)
+        corr4d, delta4d = self.forward_coarse_match(feats1[-1], feats2[-1], ksize=ksize)
+        matches_, score_ = self.cal_coarse_matches_topk(corr4d, delta4d, topk, ksize=ksize, upsample=self.upsample,
+                                                        center=True)
+        coarse_matches, _ = filter_coarse(matches_, score_, ncn_thres, mutual)
+        coarse_matches = self.shift_to_anchors(coarse_matches)
+        fine, fine_scores, mid, mid_scores = self._fine_chain(feats1, feats2, coarse_matches)
+        if return_all:
+            return fine, fine_scores, mid, mid_scores, coarse_matches
+        return fine, fine_scores, coarse_matches
 
     def coarse_async(self, feats1, feats2, ksize=2):
         """Enqueue the coarse stage of a batch and an asynchronous device-to-host copy of its

@@ -463,6 +463,33 @@ def coarse_matches(corr, delta, ksize, upsample, center=True, out_matches=None, 
     return m[0], sc[0]
 
 
+def coarse_matches_topk_batch(corr, delta, ksize, upsample, center, topk, do_softmax=True):
+    """The topk best candidates per cell and direction (corr_to_matches_topk in both directions, concatenated like
+    cal_coarse_matches): corr [B,hA',wA',hB',wB'] (+ packed delta or None) -> ([B,topk*(nB+nA),4] int64 pixel matches,
+    [B,topk*(nB+nA)] fp32 scores).  Row order and tie rule: include/p2p_hip.h.  do_softmax=False: raw consensus values."""
+    corr = _f32c(corr, "corr4d")
+    if corr.dim() != 5:
+        raise ValueError("coarse_matches_topk_batch expects corr4d of shape [B,hA,wA,hB,wB]")
+    nb, ha, wa, hb, wb = corr.shape
+    topk = int(topk)
+    n = max(topk, 0) * (ha * wa + hb * wb)
+    dev = corr.device
+    matches = torch.empty((nb, n, 4), dtype=torch.int64, device=dev)
+    scores = torch.empty((nb, n), dtype=torch.float32, device=dev)
+    if delta is not None:
+        delta = delta.contiguous()
+        if delta.dtype != torch.uint8 or delta.numel() != corr.numel():
+            raise ValueError("delta must be the packed uint8 volume with the shape of corr4d")
+    if nb == 0:
+        return matches, scores
+    with torch.cuda.device(dev):
+        _lib.check(_lib.p2p_coarse_matches_topk_batch(corr.data_ptr(), delta.data_ptr() if delta is not None else None, nb,
+                                                      ha, wa, hb, wb, ksize, upsample, int(bool(center)), topk,
+                                                      int(bool(do_softmax)), matches.data_ptr(), scores.data_ptr(), _stream()),
+                   "p2p_coarse_matches_topk_batch")
+    return matches, scores
+
+
 def filter_coarse_batch(matches, scores, ncn_thres=0.0, mutual=True):
     """filter_coarse (networks/utils.py:38-72, no ptmax) on the device for a batch: matches [B,n,4] int64, scores [B,n]
     fp32 -> (rows [B,n,4], scores [B,n], counts int32 [B]); the first counts[b] rows of item b are valid, in the
