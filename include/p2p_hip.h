@@ -57,6 +57,24 @@ void p2p_ncn_destroy(p2p_ncn *ncn);
  * cell sums its contributions in one fixed order.                                                                   */
 int p2p_ncn_set_tile(p2p_ncn *ncn, int ta, int tb, int tc);
 
+/* Any other NeighConsensus(kernel_sizes, channels, symmetric_mode) within these limits (since version 106) -- a GENERIC handle
+ * (csrc/consensus_generic.hip: exact fp32 on v_mfma_f32_16x16x4_f32, one launch per layer and branch, the hidden activations
+ * in the caller's workspace):
+ *   n_layers     1..4
+ *   kernel_size  3 or 5 per layer (cubic in all four axes, as the reference builds them)
+ *   channels     output channels per layer: 1..16 for the hidden layers, 1 for the last one (the volume is [B,1,...] downstream)
+ *   symmetric    non-zero: y = net(x) + T(net(T(x))) (model.py:149); zero: y = net(x)
+ * HOST pointers to the checkpoint tensors in their stored layout: w[i] [k, c_out, c_in, k, k, k] (conv4d.py:119-120), b[i] [c_out].
+ * Kernel sizes, channel counts or layer counts outside these lists -> P2P_EUNSUPPORTED; null pointers and counts or dims <= 0 ->
+ * P2P_EINVAL; both before the device is touched.  The released shape is accepted too (that is how the generic path is compared
+ * with the tuned one); p2p_ncn_create keeps producing tuned handles.  Every coarse entry point takes either kind;
+ * p2p_ncn_set_tile refuses a generic handle (P2P_EUNSUPPORTED).  A generic handle's results do not depend on the batch, the
+ * pair's position in it or the workspace size: every output cell sums its terms in an order the configuration alone fixes. */
+typedef struct p2p_ncn_config { int n_layers, kernel_size[4], channels[4], symmetric; } p2p_ncn_config;
+typedef struct p2p_ncn_tensors { const float *w[4], *b[4]; } p2p_ncn_tensors;
+int p2p_ncn_create_config(const p2p_ncn_config *config, const p2p_ncn_tensors *tensors, p2p_ncn **out);
+int p2p_ncn_is_generic(const p2p_ncn *ncn);      /* 1 / 0; -1 for NULL */
+
 /* FeatRegressNet with the released configuration (conv_kers [3,3], conv_strs [2,1],
  * conv_dims [512,512], fc_dims [512,256], feat_comb 'pre', psize 16, feat_idx [0,1,2,3]) --
  * reference networks/modules.py:56-112.  HOST pointers to the state_dict tensors.  These handles run the tuned kernels
@@ -150,6 +168,12 @@ int p2p_regressor_create_config(const p2p_regressor_config *config, const p2p_re
 
 /* Workspace (bytes) p2p_coarse_forward needs for these sizes (per pair); ksize 1, 2 or 4. */
 size_t p2p_coarse_workspace_bytes(int channels, int hA, int wA, int hB, int wB, int ksize);
+/* The same for a given handle: a generic handle adds the two activation buffers of its widest hidden layer (fp32, channels
+ * padded to 4, 8 or 16, per pooled cell); for a tuned handle the value above.  0 for bad arguments. */
+size_t p2p_coarse_workspace_bytes_for(const p2p_ncn *ncn, int channels, int hA, int wA, int hB, int wB, int ksize);
+/* Workspace (bytes) p2p_neigh_consensus_batch needs PER VOLUME of these sizes: 4 for a tuned handle, the activation buffers
+ * for a generic one.  0 for bad arguments. */
+size_t p2p_neigh_consensus_workspace_bytes(const p2p_ncn *ncn, int hA, int wA, int hB, int wB);
 
 /* Patch2Pix.forward_coarse_match -- reference networks/patch2pix.py:120-136:
  * L2Normalize (modules.py:6) -> FeatCorrelation (modules.py:41-53) -> maxpool4d (modules.py:11-34,
@@ -179,7 +203,11 @@ int p2p_coarse_forward_batch(const float *featA, const float *featB, int batch, 
  * y = net(x) + T(net(T(x))), net = Conv4d(1->16) + ReLU + Conv4d(16->1) + ReLU (conv4d.py:12-74), T = swap of the A and B axes,
  * on `batch` volumes x [B, hA, wA, hB, wB] (fp32) -> y_out of the same shape.  One kernel on the fp16 matrix cores in
  * fp32-equivalent arithmetic (the fp16 planes are scaled by the volume's largest magnitude, found first); the hidden
- * 16-channel volume stays in LDS (csrc/consensus.hip).  workspace: 4 bytes per volume of device memory.          */
+ * 16-channel volume stays in LDS (csrc/consensus.hip).  workspace: 4 bytes per volume of device memory.
+ * With a generic handle: the handle's own stack, layer by layer in exact fp32; the workspace must hold at least one volume's
+ * p2p_neigh_consensus_workspace_bytes (P2P_ENOMEM below that); with less than batch x that, the volumes go in groups.
+ * The workspace of a generic handle must be 16-byte aligned, here and in p2p_coarse_forward* (P2P_EINVAL otherwise: the
+ * activations are read with 16-byte loads; any hipMalloc pointer is). */
 int p2p_neigh_consensus_batch(const float *x, int batch, int hA, int wA, int hB, int wB, const p2p_ncn *ncn, float *y_out,
                               void *workspace, size_t workspace_bytes, p2p_stream_t stream);
 

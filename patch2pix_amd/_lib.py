@@ -55,6 +55,15 @@ class RegressorTensors(ctypes.Structure):
                 ("out_w", ctypes.c_void_p), ("out_b", ctypes.c_void_p)]
 
 
+class NcnConfig(ctypes.Structure):
+    _fields_ = [("n_layers", ctypes.c_int), ("kernel_size", ctypes.c_int * 4), ("channels", ctypes.c_int * 4),
+                ("symmetric", ctypes.c_int)]
+
+
+class NcnTensors(ctypes.Structure):
+    _fields_ = [("w", ctypes.c_void_p * 4), ("b", ctypes.c_void_p * 4)]
+
+
 class Pyramid(ctypes.Structure):
     _fields_ = [("level", ctypes.c_void_p * 4), ("height", ctypes.c_int), ("width", ctypes.c_int)]
 
@@ -75,6 +84,9 @@ p2p_ncn_create = _sig("p2p_ncn_create", ctypes.c_int,
                       [ctypes.c_void_p] * 4 + [ctypes.POINTER(ctypes.c_void_p)])
 p2p_ncn_destroy = _sig("p2p_ncn_destroy", None, [ctypes.c_void_p])
 p2p_ncn_set_tile = _sig("p2p_ncn_set_tile", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3)
+p2p_ncn_create_config = _sig("p2p_ncn_create_config", ctypes.c_int,
+                             [ctypes.POINTER(NcnConfig), ctypes.POINTER(NcnTensors), ctypes.POINTER(ctypes.c_void_p)])
+p2p_ncn_is_generic = _sig("p2p_ncn_is_generic", ctypes.c_int, [ctypes.c_void_p])
 p2p_regressor_create = _sig("p2p_regressor_create", ctypes.c_int,
                             [ctypes.POINTER(RegressorParams), ctypes.POINTER(ctypes.c_void_p)])
 p2p_regressor_create_config = _sig("p2p_regressor_create_config", ctypes.c_int,
@@ -82,6 +94,9 @@ p2p_regressor_create_config = _sig("p2p_regressor_create_config", ctypes.c_int,
                                     ctypes.POINTER(ctypes.c_void_p)])
 p2p_regressor_destroy = _sig("p2p_regressor_destroy", None, [ctypes.c_void_p])
 p2p_coarse_workspace_bytes = _sig("p2p_coarse_workspace_bytes", ctypes.c_size_t, [ctypes.c_int] * 6)
+p2p_coarse_workspace_bytes_for = _sig("p2p_coarse_workspace_bytes_for", ctypes.c_size_t, [ctypes.c_void_p] + [ctypes.c_int] * 6)
+p2p_neigh_consensus_workspace_bytes = _sig("p2p_neigh_consensus_workspace_bytes", ctypes.c_size_t,
+                                           [ctypes.c_void_p] + [ctypes.c_int] * 4)
 p2p_coarse_forward = _sig("p2p_coarse_forward", ctypes.c_int,
                           [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 6 +
                           [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_stream])
@@ -150,7 +165,8 @@ EXPORTS = ["p2p_version", "p2p_last_error", "p2p_ncn_create", "p2p_ncn_destroy",
            "p2p_neigh_consensus_batch", "p2p_delta_unpack", "p2p_coarse_matches", "p2p_coarse_matches_batch", "p2p_filter_coarse_workspace_bytes", "p2p_filter_coarse_batch", "p2p_match_tail_batch", "p2p_regress", "p2p_regress_workspace_bytes", "p2p_regress_workspace_bytes_mode", "p2p_regress_batch", "p2p_regress_batch_dev", "p2p_regressor_set_mode",
            "p2p_regressor_get_mode", "p2p_conv_create", "p2p_conv_destroy", "p2p_conv_set_tile", "p2p_conv_forward", "p2p_absmax_batch", "p2p_stem_create", "p2p_stem_destroy", "p2p_stem_forward",
            "p2p_maxpool_nhwc", "p2p_nhwc_to_nchw", "p2p_regressor_create_config", "p2p_regress_workspace_bytes_for",
-           "p2p_coarse_matches_topk_batch"]
+           "p2p_coarse_matches_topk_batch", "p2p_ncn_create_config", "p2p_ncn_is_generic", "p2p_coarse_workspace_bytes_for",
+           "p2p_neigh_consensus_workspace_bytes"]
 
 
 def check(status, what):

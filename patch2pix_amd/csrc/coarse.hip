@@ -534,8 +534,11 @@ static void launch_mm_apply(const float *X, int nA, int nB, const int *rkey, con
 
 // ------------------------------------------------------------------------------------------------
 // 4. neighbourhood consensus (ncn/model.py:145-155; conv4d.py:12-74): consensus.hip, one fused kernel for every
-//    volume and batch size
+//    volume and batch size (the released stack); consensus_generic.hip, one launch per layer and branch (any other stack)
 // ------------------------------------------------------------------------------------------------
+}  // namespace p2p
+#include "consensus_generic.hip"      // the shape-generic layers and their handle (no unit of its own)
+namespace p2p {
 // ------------------------------------------------------------------------------------------------
 // 5. matches (ncn/extract_ncmatches.py:6-94 twice; patch2pix.py:340-375) and their top-k form (:96-158)
 // ------------------------------------------------------------------------------------------------
@@ -762,9 +765,10 @@ __global__ void delta_unpack_kernel(const uint8_t *__restrict__ delta, size_t n,
 
 // workspace carve-up shared by the size query and the launcher
 struct CoarseWs {
-    size_t fnA, fnB, P, Y, Y2, keys, total;   // byte offsets
+    size_t fnA, fnB, P, Y, Y2, keys, act, total;   // byte offsets
 };
-static CoarseWs coarse_ws(int C, int hA, int wA, int hB, int wB, int k) {
+// gen: the generic consensus net whose activation buffers the pair's block holds as well (null: a tuned handle, none)
+static CoarseWs coarse_ws(int C, int hA, int wA, int hB, int wB, int k, const NcGen *gen = nullptr) {
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t nA = (size_t)hA * wA, nB = (size_t)hB * wB;
     const size_t nAc = nA / (k * k), nBc = nB / (k * k);
@@ -776,6 +780,8 @@ static CoarseWs coarse_ws(int C, int hA, int wA, int hB, int wB, int k) {
     w.Y = off; off += al(nAc * nBc * 4);     // the two branches of the consensus net
     w.Y2 = off; off += al(nAc * nBc * 4);
     w.keys = off; off += al((2 * (nAc + nBc) + 1) * 4);      // row / column maxima of both mutual matchings + max |X|
+    w.act = off;
+    if (gen) off += nc_generic_ws_bytes(*gen, nAc * nBc);
     w.total = off;
     return w;
 }
@@ -809,12 +815,29 @@ extern "C" int p2p_ncn_create(const float *w1, const float *b1, const float *w2,
     n->b2 = b2[0];
     n->wfused = wfd;
     n->tile[0] = n->tile[1] = n->tile[2] = 0;
+    n->gen = nullptr;
     *out = n;
     return P2P_OK;
 }
 
+extern "C" int p2p_ncn_create_config(const p2p_ncn_config *config, const p2p_ncn_tensors *tensors, p2p_ncn **out) {
+    P2P_REQUIRE(out, P2P_EINVAL, "p2p_ncn_create_config: null argument");
+    NcGen *g = nullptr;
+    const int st = nc_generic_create(config, tensors, &g);      // validates before it touches the device
+    if (st != P2P_OK) return st;
+    p2p_ncn *n = new p2p_ncn();
+    n->b2 = 0.f; n->wfused = nullptr;
+    n->tile[0] = n->tile[1] = n->tile[2] = 0;
+    n->gen = g;
+    *out = n;
+    return P2P_OK;
+}
+
+extern "C" int p2p_ncn_is_generic(const p2p_ncn *ncn) { return ncn ? (ncn->gen ? 1 : 0) : -1; }
+
 extern "C" int p2p_ncn_set_tile(p2p_ncn *ncn, int ta, int tb, int tc) {
     P2P_REQUIRE(ncn && ta >= 0 && tb >= 0 && tc >= 0, P2P_EINVAL, "p2p_ncn_set_tile: bad argument");
+    P2P_REQUIRE(!ncn->gen, P2P_EUNSUPPORTED, "p2p_ncn_set_tile: a generic consensus handle has no work-group tile to force");
     // (0, 0, 0) = automatic; (ta, tb, tc) with tb, tc > 0 = forced (ta = 0: only the march length is picked); anything else
     // would be ignored silently
     P2P_REQUIRE((tb > 0 && tc > 0) || (ta == 0 && tb == 0 && tc == 0), P2P_EINVAL,
@@ -825,13 +848,24 @@ extern "C" int p2p_ncn_set_tile(p2p_ncn *ncn, int ta, int tb, int tc) {
 
 extern "C" void p2p_ncn_destroy(p2p_ncn *ncn) {
     if (!ncn) return;
-    (void)hipFree(ncn->wfused);
+    if (ncn->wfused) (void)hipFree(ncn->wfused);
+    nc_generic_destroy(ncn->gen);
     delete ncn;
 }
 
 extern "C" size_t p2p_coarse_workspace_bytes(int channels, int hA, int wA, int hB, int wB, int ksize) {
     if (channels <= 0 || hA <= 0 || wA <= 0 || hB <= 0 || wB <= 0 || ksize < 1) return 0;
     return coarse_ws(channels, hA, wA, hB, wB, ksize).total;
+}
+
+extern "C" size_t p2p_coarse_workspace_bytes_for(const p2p_ncn *ncn, int channels, int hA, int wA, int hB, int wB, int ksize) {
+    if (!ncn || channels <= 0 || hA <= 0 || wA <= 0 || hB <= 0 || wB <= 0 || ksize < 1) return 0;
+    return coarse_ws(channels, hA, wA, hB, wB, ksize, ncn->gen).total;
+}
+
+extern "C" size_t p2p_neigh_consensus_workspace_bytes(const p2p_ncn *ncn, int hA, int wA, int hB, int wB) {
+    if (!ncn || hA <= 0 || wA <= 0 || hB <= 0 || wB <= 0) return 0;
+    return ncn->gen ? nc_generic_ws_bytes(*ncn->gen, (size_t)hA * wA * hB * wB) : sizeof(int);
 }
 
 extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, int batch, int C, int hA, int wA, int hB,
@@ -844,9 +878,16 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
     P2P_REQUIRE(C > 0 && C % 32 == 0 && C <= 256, P2P_EUNSUPPORTED, "p2p_coarse_forward: channels %d (multiple of 32, <= 256)", C);
     P2P_REQUIRE(hA > 0 && wA > 0 && hB > 0 && wB > 0 && hA % ksize == 0 && wA % ksize == 0 && hB % ksize == 0 &&
                     wB % ksize == 0, P2P_EINVAL, "p2p_coarse_forward: feature map sizes must be positive multiples of ksize");
-    const CoarseWs ws = coarse_ws(C, hA, wA, hB, wB, ksize);
+    // The handle is dereferenced only after the workspace has passed the size every kind of handle needs: callers probe this
+    // entry point's argument checks with placeholder handles (tests/test_cabi_exports.py::test_batch_argument_errors passes
+    // ncn = 1 with a 64-byte workspace and expects the workspace error, as before generic handles existed).
+    const size_t ws_any = coarse_ws(C, hA, wA, hB, wB, ksize).total;
+    P2P_REQUIRE(workspace_bytes >= ws_any, P2P_ENOMEM, "p2p_coarse_forward: workspace %zu < %zu bytes (one pair)", workspace_bytes, ws_any);
+    const CoarseWs ws = coarse_ws(C, hA, wA, hB, wB, ksize, ncn->gen);
     P2P_REQUIRE(workspace_bytes >= ws.total, P2P_ENOMEM, "p2p_coarse_forward: workspace %zu < %zu bytes (one pair)", workspace_bytes,
                 ws.total);
+    P2P_REQUIRE(!ncn->gen || ((uintptr_t)workspace & 15) == 0, P2P_EINVAL,
+                "p2p_coarse_forward: the workspace of a generic handle must be 16-byte aligned");
     const int nA = hA * wA, nB = hB * wB, kk = ksize * ksize;
     const int nAc = nA / kk, nBc = nB / kk;
     const size_t nel = (size_t)nAc * nBc;
@@ -910,7 +951,11 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
 
         // first mutual matching, in place on the pooled volume (+ max |X| for the consensus kernel's operand scale)
         launch_mm_apply(P, nAc, nBc, rkey1, ckey1, P, sWs, sWs, sWs, xmax, nullptr, nz, stream);
-        {   // both consensus layers, both branches: relu(.) of the direct branch into Y, of the transposed one into Y2
+        if (ncn->gen) {   // a generic stack: layer by layer, the sum of its branches in Y
+            const int st = launch_nc_generic(*ncn->gen, P, sWs, Y, sWs, (float *)(base + ws.act), sWs, (int)nz, d0, d1, d2, d3, stream);
+            if (st != P2P_OK) return st;
+            Y2 = nullptr;
+        } else {   // both consensus layers, both branches: relu(.) of the direct branch into Y, of the transposed one into Y2
             const int st = launch_nc_fused(P, Y, Y2, sWs, (int)nz, d0, d1, d2, d3, ncn->wfused, ncn->b2, xmax, sWs, ncn->tile, stream);
             if (st != P2P_OK) return st;
         }
@@ -932,6 +977,18 @@ extern "C" int p2p_neigh_consensus_batch(const float *x, int batch, int hA, int 
     hipStream_t stream = (hipStream_t)stream_;
     P2P_REQUIRE(x && ncn && y_out && workspace, P2P_EINVAL, "p2p_neigh_consensus: null argument");
     P2P_REQUIRE(batch >= 1 && batch <= 65535 && hA > 0 && wA > 0 && hB > 0 && wB > 0, P2P_EINVAL, "p2p_neigh_consensus: bad sizes");
+    if (ncn->gen) {
+        const size_t cells = (size_t)hA * wA * hB * wB, per = nc_generic_ws_bytes(*ncn->gen, cells);
+        P2P_REQUIRE(workspace_bytes >= per, P2P_ENOMEM, "p2p_neigh_consensus: workspace %zu < %zu bytes (one volume)", workspace_bytes, per);
+        P2P_REQUIRE(((uintptr_t)workspace & 15) == 0, P2P_EINVAL, "p2p_neigh_consensus: the workspace of a generic handle must be 16-byte aligned");
+        const int per_launch = (int)std::min<size_t>(batch, workspace_bytes / per);      // volumes the workspace holds at once
+        for (int z0 = 0; z0 < batch; z0 += per_launch) {
+            const int st = launch_nc_generic(*ncn->gen, x + (size_t)z0 * cells, cells, y_out + (size_t)z0 * cells, cells, (float *)workspace,
+                                             per / sizeof(float), std::min(per_launch, batch - z0), hA, wA, hB, wB, stream);
+            if (st != P2P_OK) return st;
+        }
+        return P2P_OK;
+    }
     P2P_REQUIRE(workspace_bytes >= (size_t)batch * sizeof(int), P2P_ENOMEM, "p2p_neigh_consensus: workspace of %zu bytes needed (4 per volume)",
                 (size_t)batch * sizeof(int));
     const size_t nel = (size_t)hA * wA * hB * wB;

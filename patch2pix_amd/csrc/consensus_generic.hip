@@ -1,0 +1,256 @@
+// Coarse stage, shape-generic path: every NeighConsensus stack within the limits of include/p2p_hip.h (p2p_ncn_config), exact
+// fp32 on the matrix cores.  The tuned kernel (consensus.hip) is built around 1 -> 16 -> 1 channels and 3^4 taps with the hidden
+// volume in LDS; this file trades that fusion for generality: one launch per layer and branch over the volumes of a call, the
+// hidden activations in the caller's workspace as fp32 [pair][a][b][c][d][channel], channels innermost and padded to 4, 8 or 16.
+//
+// A layer is a "same" 4-D cross-correlation (conv4d.py:12-74: zero padding k / 2 on all four axes, bias, ReLU) as an implicit
+// GEMM on v_mfma_f32_16x16x4_f32: rows = 16 consecutive cells along the innermost axis d, columns = the up-to-16 output
+// channels (zero-padded to 16), K = (tap, input channel), taps outer in the order (da, db, dc, dd).  A super-step is four MFMAs
+// = 16 K values; lane (row, kb = lane >> 4) supplies value j of MFMA j:
+//   first layer (one input channel, the caller's volume):  tap 16 S + 4 kb + j             -- four 4-byte loads
+//   other layers (CP = 4, 8 or 16 padded channels):        tap (4 / Q) S + kb / Q, channels 4 (kb % Q) + j, Q = CP / 4
+//                                                                                          -- one 16-byte load
+// Taps past the last one and channels past the last one meet zero weights.  A tap outside the volume contributes zeros: the
+// address is clamped into the volume, the load is unconditional and the zero is selected when the value is used.
+// The transposed branch of symmetric_mode, T(net(T(x))), reads the same volume in the same cell order: in x's coordinates the
+// weight of offset (da, db, dc, dd) is w[dc][dd][da][db], so only the packing differs (gen_nc_pack); no permuted copy exists.
+// The direct branch's last layer stores y, the transposed branch's last layer adds to it (plain read-add-write: one lane per
+// word, launches of one stream run in order).  Every output sums its K terms super-step by super-step, j = 0..3: the order
+// depends on the configuration alone -- not on the pair's position in the batch, the batch size or the workspace.
+// Device code is restricted to what the kernel emulator of the test-suite runs.  Compiled as part of coarse.hip.
+#pragma once
+#include "p2p_common.h"
+
+#include <algorithm>
+#include <vector>
+
+namespace p2p {
+
+#define P2P_NCG_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+
+constexpr int NCG_MAX_LAYERS = 4;
+constexpr int NCG_MAX_TAPS = 640;          // 5^4 = 625, rounded up to whole super-steps of 16 taps
+
+struct NcGenLayer {
+    int k, ci, co;           // kernel side, input / output channels
+    int cpi, cpo;            // padded channels of the input / output activations (input of layer 0: 1; output of the last: 1)
+    int nsteps;              // super-steps of 16 K values
+    const float *w[2];       // B fragments [step][lane][4] of the direct / transposed branch
+    const float *bias;       // [16], zero past co
+};
+
+struct NcGen {
+    int n_layers, symmetric, cpmax;
+    NcGenLayer layer[NCG_MAX_LAYERS];
+    float *mem;              // one device allocation: every layer's fragments and biases
+};
+
+struct NcGenArgs {
+    const float *in;         // [pair][cells][cpi]
+    float *out;              // [pair][cells][cpo]
+    size_t s_in, s_out;      // floats between pairs
+    const float *w, *bias;
+    int d0, d1, d2, d3, nd;  // the volume, tiles of 16 cells per row of d
+    int k, cpi, cpo, nsteps;
+    int tiles;               // per pair
+    int add;                 // last layer of the transposed branch: out += result
+};
+
+__device__ __forceinline__ int ncg_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// FIRST: the layer reads the caller's one-channel volume (cpi == 1)
+template <bool FIRST>
+__global__ __launch_bounds__(256) void nc_generic_kernel(NcGenArgs a) {
+    __shared__ int taps[NCG_MAX_TAPS];       // (da, db, dc, dd) of a tap, one byte each; taps past the last repeat it (zero weights)
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, kb = lane >> 4;
+    const int k = a.k, ntap = k * k * k * k;
+    for (int t = tid; t < NCG_MAX_TAPS; t += 256) {
+        const int u = min(t, ntap - 1);
+        taps[t] = ((u / (k * k * k)) << 24) | (((u / (k * k)) % k) << 16) | (((u / k) % k) << 8) | (u % k);
+    }
+    __syncthreads();
+    const int tile = blockIdx.x * 4 + wave;
+    if (tile >= a.tiles) return;              // (whole waves, behind the only barrier)
+    int g = tile;
+    const int dt0 = (g % a.nd) * 16; g /= a.nd;
+    const int c = g % a.d2; g /= a.d2;
+    const int b = g % a.d1;
+    const int aa = g / a.d1;
+    const int pad = k >> 1;
+    const float *in = a.in + (size_t)blockIdx.z * a.s_in;
+    float *out = a.out + (size_t)blockIdx.z * a.s_out;
+    const int d = dt0 + l15;                 // this lane's cell of the row (rows past the volume multiply clamped copies)
+    const float *wl = a.w + (size_t)lane * 4;
+
+    // the value(s) of one tap for this lane: clamped address, and whether the tap lies inside the volume
+    auto locate = [&](int tap, bool *ok) {
+        const int tp = taps[tap];
+        const int ia = aa + (tp >> 24) - pad, ib = b + ((tp >> 16) & 255) - pad, ic = c + ((tp >> 8) & 255) - pad, id = d + (tp & 255) - pad;
+        *ok = ia >= 0 && ia < a.d0 && ib >= 0 && ib < a.d1 && ic >= 0 && ic < a.d2 && id >= 0 && id < a.d3;
+        return (size_t)((ncg_clamp(ia, a.d0 - 1) * a.d1 + ncg_clamp(ib, a.d1 - 1)) * a.d2 + ncg_clamp(ic, a.d2 - 1)) * a.d3 + ncg_clamp(id, a.d3 - 1);
+    };
+
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (FIRST) {
+        for (int S = 0; S < a.nsteps; ++S) {
+            f32x4 av;
+            bool ok[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) av[j] = in[locate(16 * S + 4 * kb + j, &ok[j])];
+            const f32x4 bv = *(const f32x4 *)(wl + (size_t)S * 256);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = P2P_NCG_MFMA(ok[j] ? av[j] : 0.f, bv[j], acc);
+        }
+    } else {
+        const int Q = a.cpi >> 2, tps = 4 / Q;                   // quads of channels per cell; taps per super-step
+        const int tsub = kb / Q, coff = 4 * (kb - tsub * Q);
+        for (int S = 0; S < a.nsteps; ++S) {
+            bool ok;
+            const size_t cell = locate(tps * S + tsub, &ok);
+            const f32x4 ld = *(const f32x4 *)(in + cell * a.cpi + coff);
+            const f32x4 bv = *(const f32x4 *)(wl + (size_t)S * 256);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = P2P_NCG_MFMA(ok ? ld[j] : 0.f, bv[j], acc);
+        }
+    }
+    // accumulator register r = cell dt0 + 4 kb + r of the row, column l15 = output channel
+    if (l15 >= a.cpo) return;
+    const float bias = a.bias[l15];
+    const size_t row0 = (size_t)((aa * a.d1 + b) * a.d2 + c) * a.d3;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int od = dt0 + 4 * kb + r;
+        if (od >= a.d3) continue;
+        float *dst = out + (row0 + od) * a.cpo + l15;
+        const float v = fmaxf(acc[r] + bias, 0.f);
+        *dst = a.add ? *dst + v : v;
+    }
+}
+
+// ---- host: packing, the handle, the launches -----------------------------------------------------------------------------------
+static int ncg_pad_channels(int c) { return c <= 4 ? 4 : (c <= 8 ? 8 : 16); }
+
+// stored weight [k(da)][co][ci][k(db)][k(dc)][k(dd)] (conv4d.py:119-120) -> B fragments out[(S * 64 + lane) * 4 + j] of branch br
+// in the K order of nc_generic_kernel; column n = lane & 15 is output channel n
+static void gen_nc_pack(const float *w, const NcGenLayer &L, bool first, int br, float *out) {
+    const int k = L.k, ntap = k * k * k * k;
+    auto W = [&](int o, int i, int da, int db, int dc, int dd) {
+        return w[((((size_t)(da * L.co + o) * L.ci + i) * k + db) * k + dc) * k + dd];
+    };
+    const int Q = L.cpi / 4;
+    for (int S = 0; S < L.nsteps; ++S)
+        for (int lane = 0; lane < 64; ++lane)
+            for (int j = 0; j < 4; ++j) {
+                const int n = lane & 15, kb = lane >> 4;
+                const int tap = first ? 16 * S + 4 * kb + j : (4 / Q) * S + kb / Q;
+                const int ch = first ? 0 : 4 * (kb % Q) + j;
+                float v = 0.f;
+                if (tap < ntap && ch < L.ci && n < L.co) {
+                    const int da = tap / (k * k * k), db = (tap / (k * k)) % k, dc = (tap / k) % k, dd = tap % k;
+                    v = br ? W(n, ch, dc, dd, da, db) : W(n, ch, da, db, dc, dd);
+                }
+                out[((size_t)S * 64 + lane) * 4 + j] = v;
+            }
+}
+
+int nc_generic_create(const p2p_ncn_config *cfg, const p2p_ncn_tensors *t, NcGen **out) {
+    const char *F = "p2p_ncn_create_config";
+    P2P_REQUIRE(cfg && t && out, P2P_EINVAL, "%s: null argument", F);
+    P2P_REQUIRE(cfg->n_layers >= 1, P2P_EINVAL, "%s: n_layers %d must be positive", F, cfg->n_layers);
+    P2P_REQUIRE(cfg->n_layers <= NCG_MAX_LAYERS, P2P_EUNSUPPORTED, "%s: n_layers %d: at most 4 layers are implemented", F, cfg->n_layers);
+    for (int i = 0; i < cfg->n_layers; ++i) {
+        const int k = cfg->kernel_size[i], c = cfg->channels[i];
+        P2P_REQUIRE(k > 0 && c > 0, P2P_EINVAL, "%s: kernel_size / channels [%d] = %d / %d must be positive", F, i, k, c);
+        P2P_REQUIRE(k == 3 || k == 5, P2P_EUNSUPPORTED, "%s: kernel_size[%d] = %d: kernel sizes 3 and 5 are implemented", F, i, k);
+        P2P_REQUIRE(c <= 16, P2P_EUNSUPPORTED, "%s: channels[%d] = %d: at most 16 channels are implemented", F, i, c);
+    }
+    P2P_REQUIRE(cfg->channels[cfg->n_layers - 1] == 1, P2P_EUNSUPPORTED, "%s: the last layer has %d channels: the consensus volume has one", F,
+                cfg->channels[cfg->n_layers - 1]);
+    for (int i = 0; i < cfg->n_layers; ++i)
+        P2P_REQUIRE(t->w[i] && t->b[i], P2P_EINVAL, "%s: null pointer among the tensors of layer %d", F, i);
+
+    NcGen *g = new NcGen();
+    g->n_layers = cfg->n_layers; g->symmetric = cfg->symmetric != 0; g->cpmax = 0; g->mem = nullptr;
+    const int nbr = g->symmetric ? 2 : 1;
+    size_t off = 0, o_w[NCG_MAX_LAYERS][2], o_b[NCG_MAX_LAYERS];
+    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~size_t(63); return o; };
+    for (int i = 0; i < g->n_layers; ++i) {
+        NcGenLayer &L = g->layer[i];
+        const bool last = i + 1 == g->n_layers;
+        L.k = cfg->kernel_size[i]; L.ci = i ? cfg->channels[i - 1] : 1; L.co = cfg->channels[i];
+        L.cpi = i ? g->layer[i - 1].cpo : 1;
+        L.cpo = last ? 1 : ncg_pad_channels(L.co);
+        if (!last) g->cpmax = std::max(g->cpmax, L.cpo);
+        const int ntap = L.k * L.k * L.k * L.k;
+        L.nsteps = i ? ceil_div(ntap * L.cpi, 16) : ceil_div(ntap, 16);
+        for (int br = 0; br < nbr; ++br) o_w[i][br] = take((size_t)L.nsteps * 256);
+        o_b[i] = take(16);
+    }
+    std::vector<float> h(off, 0.f);
+    for (int i = 0; i < g->n_layers; ++i) {
+        const NcGenLayer &L = g->layer[i];
+        for (int br = 0; br < nbr; ++br) gen_nc_pack(t->w[i], L, i == 0, br, &h[o_w[i][br]]);
+        for (int q = 0; q < L.co; ++q) h[o_b[i] + q] = t->b[i][q];
+    }
+    hipError_t e = hipMalloc(&g->mem, h.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(g->mem, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        set_error("%s: uploading the packed consensus net failed: %s", F, hipGetErrorString(e));
+        if (g->mem) (void)hipFree(g->mem);
+        delete g;
+        return P2P_EHIP;
+    }
+    for (int i = 0; i < g->n_layers; ++i) {
+        NcGenLayer &L = g->layer[i];
+        L.w[0] = g->mem + o_w[i][0];
+        L.w[1] = g->symmetric ? g->mem + o_w[i][1] : nullptr;
+        L.bias = g->mem + o_b[i];
+    }
+    *out = g;
+    return P2P_OK;
+}
+
+void nc_generic_destroy(NcGen *g) {
+    if (!g) return;
+    if (g->mem) (void)hipFree(g->mem);
+    delete g;
+}
+
+// scratch of one volume: the two activation buffers layers alternate between (a single layer needs none: one block)
+size_t nc_generic_ws_bytes(const NcGen &g, size_t cells) {
+    return std::max<size_t>(256, (2 * cells * g.cpmax * sizeof(float) + 255) & ~size_t(255));
+}
+
+// NeighConsensus.forward for `pairs` volumes: X / Y / act of pair z sit z * s_x / s_y / s_act floats further on
+int launch_nc_generic(const NcGen &g, const float *X, size_t s_x, float *Y, size_t s_y, float *act, size_t s_act, int pairs,
+                      int d0, int d1, int d2, int d3, hipStream_t stream) {
+    // cell offsets are computed in 32 bits
+    P2P_REQUIRE((unsigned long long)d0 * d1 * d2 * d3 < (1ull << 31), P2P_EUNSUPPORTED,
+                "consensus volume %d x %d x %d x %d has 2^31 cells or more", d0, d1, d2, d3);
+    const size_t cells = (size_t)d0 * d1 * d2 * d3;
+    float *buf[2] = {act, act + cells * g.cpmax};
+    NcGenArgs a{};
+    a.d0 = d0; a.d1 = d1; a.d2 = d2; a.d3 = d3; a.nd = ceil_div(d3, 16);
+    const long long tiles = (long long)d0 * d1 * d2 * a.nd;
+    P2P_REQUIRE(tiles < (1ll << 31) - 4, P2P_EUNSUPPORTED, "consensus volume: %lld row tiles in one launch", tiles);
+    a.tiles = (int)tiles;
+    const dim3 grid((unsigned)((tiles + 3) / 4), 1, (unsigned)pairs);
+    for (int br = 0; br < (g.symmetric ? 2 : 1); ++br)
+        for (int i = 0; i < g.n_layers; ++i) {
+            const NcGenLayer &L = g.layer[i];
+            const bool last = i + 1 == g.n_layers;
+            a.in = i ? buf[(i - 1) & 1] : X; a.s_in = i ? s_act : s_x;
+            a.out = last ? Y : buf[i & 1]; a.s_out = last ? s_y : s_act;
+            a.w = L.w[br]; a.bias = L.bias;
+            a.k = L.k; a.cpi = L.cpi; a.cpo = L.cpo; a.nsteps = L.nsteps;
+            a.add = last && br == 1;
+            if (i == 0) hipLaunchKernelGGL(nc_generic_kernel<true>, grid, dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL(nc_generic_kernel<false>, grid, dim3(256), 0, stream, a);
+            const int st = check_launch("nc_generic_kernel");
+            if (st != P2P_OK) return st;
+        }
+    return P2P_OK;
+}
+
+}  // namespace p2p

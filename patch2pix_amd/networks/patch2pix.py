@@ -51,8 +51,24 @@ def _regressor_spec(layout):
     return spec
 
 
-_NCN_SPEC = {"conv.0.weight": ((3, 16, 1, 3, 3, 3), "param"), "conv.0.bias": ((16,), "param"),
-             "conv.2.weight": ((3, 1, 16, 3, 3, 3), "param"), "conv.2.bias": ((1,), "param")}
+def _ncn_spec(layout):
+    """Keys and shapes of the reference's NeighConsensus (networks/ncn/model.py:124-143, filters in the stored layout of
+    conv4d.py:119-120) for a checked stack (ops.ncn_layout)."""
+    return {k: (shp, "param") for k, shp in ops.ncn_shapes(layout).items()}
+
+
+def _ncn_layout_of(config):
+    """`config.ncn_config` (namespace or dict: kernel_sizes, channels, optionally symmetric_mode) if present; else the stack
+    the checkpoint's ncn.conv.* tensors have; else the released one."""
+    nc = getattr(config, "ncn_config", None)
+    if nc is not None:
+        return ops.ncn_layout(nc)
+    wd = getattr(config, "weights_dict", None) or {}
+    sub = {k[len("ncn."):]: v for k, v in wd.items() if k.startswith("ncn.conv.")}
+    return ops.ncn_layout(sub if sub else None)
+
+
+_NCN_SPEC = _ncn_spec(ops.RELEASED_NCN_LAYOUT)
 
 
 class Delta4d:
@@ -103,7 +119,9 @@ class Patch2Pix(nn.Module):
             self.feats_downsample[-1] = 1
         else:
             raise NotImplementedError("change_stride=False (upsample 16) is not implemented by the HIP fine stage")
-        self.ncn = _Holder(_NCN_SPEC)
+        # what the library implements (include/p2p_hip.h, p2p_ncn_config): NotImplementedError / ValueError otherwise
+        self._ncn_layout = _ncn_layout_of(config)
+        self.ncn = _Holder(_ncn_spec(self._ncn_layout))
 
         self.regressor_config = config.regressor_config
         self.regress_mid = None
@@ -155,8 +173,8 @@ class Patch2Pix(nn.Module):
         """Pack (BN folding, MFMA fragment order, transposed-branch filters) once per weight load."""
         if self._packed is None:
             sd = self.state_dict()
-            ncn = ops.NcnWeights(sd["ncn.conv.0.weight"], sd["ncn.conv.0.bias"], sd["ncn.conv.2.weight"],
-                                 sd["ncn.conv.2.bias"], self.device)
+            ncn = ops.NcnWeights.from_state_dict({k[len("ncn."):]: v for k, v in sd.items() if k.startswith("ncn.")}, self.device,
+                                                 symmetric_mode=self._ncn_layout["symmetric_mode"])
             mid = fine = None
             if self.regress_mid is not None:
                 sub = lambda p: {k[len(p):]: v for k, v in sd.items() if k.startswith(p)}

@@ -23,8 +23,71 @@ def _host(t):
     return t.detach().to("cpu", torch.float32).contiguous()
 
 
+RELEASED_NCN_LAYOUT = dict(kernel_sizes=[3, 3], channels=[16, 1], symmetric_mode=True)
+NCN_MAX_LAYERS, NCN_KERNEL_SIZES, NCN_MAX_CHANNELS = 4, (3, 5), 16       # include/p2p_hip.h, p2p_ncn_config
+
+
+def ncn_layout(source=None, symmetric_mode=None):
+    """The NeighConsensus stack (reference networks/ncn/model.py:124-143) a checkpoint or a configuration describes, as
+    dict(kernel_sizes, channels, symmetric_mode) of plain lists, checked against what the library implements.  `source`:
+    a sub-state_dict ('conv.{2i}.weight' in the stored layout [k, c_out, c_in, k, k, k], conv4d.py:119-120) whose shapes
+    are read, a namespace or dict with kernel_sizes / channels (/ symmetric_mode), or None (the released stack).  A stack
+    the reference accepts and the library does not raises NotImplementedError, a malformed one ValueError; no GPU needed."""
+    if source is None:
+        lay = {k: (list(v) if isinstance(v, list) else v) for k, v in RELEASED_NCN_LAYOUT.items()}
+    elif isinstance(source, dict) and any(str(k).startswith("conv.") for k in source):
+        ks, ch, cin, i = [], [], 1, 0
+        while f"conv.{2 * i}.weight" in source:
+            shp = tuple(source[f"conv.{2 * i}.weight"].shape)
+            if len(shp) != 6 or len({shp[0], shp[3], shp[4], shp[5]}) != 1:
+                raise ValueError(f"conv.{2 * i}.weight has shape {shp}: expected the stored layout [k, c_out, c_in, k, k, k]")
+            if shp[2] != cin:
+                raise ValueError(f"conv.{2 * i}.weight has {shp[2]} input channels where the layer below it gives {cin}")
+            bias = source.get(f"conv.{2 * i}.bias")
+            if bias is None or tuple(bias.shape) != (shp[1],):
+                raise ValueError(f"conv.{2 * i}.bias is missing or is not of shape ({shp[1]},)")
+            ks.append(int(shp[0])); ch.append(int(shp[1])); cin = shp[1]; i += 1
+        if not ks:
+            raise ValueError("no conv.0.weight among the consensus tensors")
+        lay = dict(kernel_sizes=ks, channels=ch, symmetric_mode=True)
+    else:
+        get = (lambda k, d=None: source.get(k, d)) if isinstance(source, dict) else (lambda k, d=None: getattr(source, k, d))
+        ks, ch = get("kernel_sizes"), get("channels")
+        if ks is None or ch is None:
+            raise ValueError("a consensus configuration needs kernel_sizes and channels")
+        lay = dict(kernel_sizes=[int(k) for k in ks], channels=[int(c) for c in ch], symmetric_mode=bool(get("symmetric_mode", True)))
+    if symmetric_mode is not None:
+        lay["symmetric_mode"] = bool(symmetric_mode)
+    ks, ch = lay["kernel_sizes"], lay["channels"]
+    if not ks or len(ks) != len(ch):
+        raise ValueError(f"kernel_sizes {ks} and channels {ch} must be non-empty lists of one length")
+    if any(k <= 0 for k in ks) or any(c <= 0 for c in ch):
+        raise ValueError(f"kernel_sizes {ks} / channels {ch}: sizes must be positive")
+    if len(ks) > NCN_MAX_LAYERS:
+        raise NotImplementedError(f"kernel_sizes {ks}: at most {NCN_MAX_LAYERS} consensus layers are implemented")
+    if any(k not in NCN_KERNEL_SIZES for k in ks):
+        raise NotImplementedError(f"kernel_sizes {ks}: kernel sizes 3 and 5 are implemented")
+    if any(c > NCN_MAX_CHANNELS for c in ch):
+        raise NotImplementedError(f"channels {ch}: at most {NCN_MAX_CHANNELS} channels per layer are implemented")
+    if ch[-1] != 1:
+        raise NotImplementedError(f"channels {ch}: the last layer must have one channel (the volume is [B,1,...] downstream)")
+    return lay
+
+
+def ncn_shapes(lay):
+    """State_dict keys -> shapes of the NeighConsensus of an `ncn_layout` in the stored layout (conv4d.py:119-120)."""
+    shapes, cin = {}, 1
+    for i, (k, c) in enumerate(zip(lay["kernel_sizes"], lay["channels"])):
+        shapes[f"conv.{2 * i}.weight"], shapes[f"conv.{2 * i}.bias"] = (k, c, cin, k, k, k), (c,)
+        cin = c
+    return shapes
+
+
 class NcnWeights:
-    """Device-resident NeighConsensus filters (reference networks/ncn/model.py:124-143)."""
+    """Device-resident NeighConsensus filters (reference networks/ncn/model.py:124-143).  The constructor takes the released
+    stack's four tensors (the tuned kernel); `from_state_dict` takes any stack within `ncn_layout`'s limits."""
+
+    layout, generic = RELEASED_NCN_LAYOUT, False
 
     def __init__(self, w1, b1, w2, b2, device):
         keep = [_host(w1), _host(b1), _host(w2), _host(b2)]
@@ -35,8 +98,32 @@ class NcnWeights:
             _lib.check(_lib.p2p_ncn_create(*[t.data_ptr() for t in keep], ctypes.byref(self.handle)), "p2p_ncn_create")
         self.device = torch.device(device)
 
+    @classmethod
+    def from_state_dict(cls, sd, device, symmetric_mode=True, generic=False):
+        """`sd`: the sub-state_dict of the consensus net ('conv.0.weight', 'conv.0.bias', 'conv.2.weight', ...).  The released
+        stack with symmetric_mode and without `generic` runs the tuned kernel; every other one -- or `generic=True` -- a
+        generic handle (p2p_ncn_create_config: exact fp32 MFMA, one launch per layer and branch)."""
+        lay = ncn_layout({k: v for k, v in sd.items() if k.startswith("conv.")}, symmetric_mode)
+        if not generic and lay == RELEASED_NCN_LAYOUT:
+            return cls(sd["conv.0.weight"], sd["conv.0.bias"], sd["conv.2.weight"], sd["conv.2.bias"], device)
+        n = len(lay["kernel_sizes"])
+        keep = [(_host(sd[f"conv.{2 * i}.weight"]), _host(sd[f"conv.{2 * i}.bias"])) for i in range(n)]
+        c, t = _lib.NcnConfig(), _lib.NcnTensors()
+        c.n_layers, c.symmetric = n, int(lay["symmetric_mode"])
+        for i in range(n):
+            c.kernel_size[i], c.channels[i] = lay["kernel_sizes"][i], lay["channels"][i]
+            t.w[i], t.b[i] = keep[i][0].data_ptr(), keep[i][1].data_ptr()
+        self = cls.__new__(cls)
+        self.handle = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(_lib.p2p_ncn_create_config(ctypes.byref(c), ctypes.byref(t), ctypes.byref(self.handle)), "p2p_ncn_create_config")
+        self.device, self.layout, self.generic = torch.device(device), lay, True
+        return self
+
     def set_tile(self, ta=0, tb=0, tc=0):
         """Force the work-group tile of the consensus kernel (tests, sweeps); (0, 0, 0) = automatic.  Results do not depend on it."""
+        if self.generic:
+            raise NotImplementedError("set_tile: a generic consensus handle has no work-group tile to force")
         _lib.check(_lib.p2p_ncn_set_tile(self.handle, int(ta), int(tb), int(tc)), "p2p_ncn_set_tile")
 
     def __del__(self):
@@ -381,7 +468,7 @@ def coarse_forward_batch(feat_a, feat_b, ksize, ncn, want_delta=True, out_corr=N
     if nb == 0:
         return corr, delta
     with torch.cuda.device(dev):
-        per_pair = _lib.p2p_coarse_workspace_bytes(c, ha, wa, hb, wb, ksize)
+        per_pair = _lib.p2p_coarse_workspace_bytes_for(ncn.handle, c, ha, wa, hb, wb, ksize)
         if per_pair == 0:
             raise ValueError("coarse_forward: bad sizes")
         pairs = max(1, min(nb, COARSE_WORKSPACE_LIMIT // per_pair))
@@ -404,7 +491,8 @@ def coarse_forward(feat_a, feat_b, ksize, ncn, want_delta=True, out_corr=None, o
 
 def neigh_consensus_batch(x, ncn):
     """NeighConsensus.forward (reference networks/ncn/model.py:145-155) on a batch of volumes x [B,hA,wA,hB,wB] fp32 GPU
-    -> the same shape: both consensus layers and both symmetric branches in one kernel (csrc/consensus.hip)."""
+    -> the same shape: both consensus layers and both symmetric branches in one kernel (csrc/consensus.hip), or a generic
+    handle's stack layer by layer (csrc/consensus_generic.hip)."""
     x = _f32c(x, "x")
     if x.dim() != 5:
         raise ValueError("neigh_consensus_batch expects [B,hA,wA,hB,wB]")
@@ -413,8 +501,10 @@ def neigh_consensus_batch(x, ncn):
     if nb == 0 or x.numel() == 0:
         return y
     with torch.cuda.device(x.device):
-        ws = torch.empty(nb, dtype=torch.int32, device=x.device)
-        _lib.check(_lib.p2p_neigh_consensus_batch(x.data_ptr(), nb, ha, wa, hb, wb, ncn.handle, y.data_ptr(), ws.data_ptr(), nb * 4,
+        per = _lib.p2p_neigh_consensus_workspace_bytes(ncn.handle, ha, wa, hb, wb)
+        nbytes = per * max(1, min(nb, COARSE_WORKSPACE_LIMIT // per))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(_lib.p2p_neigh_consensus_batch(x.data_ptr(), nb, ha, wa, hb, wb, ncn.handle, y.data_ptr(), ws.data_ptr(), nbytes,
                                                   _stream()), "p2p_neigh_consensus_batch")
     return y
 

@@ -93,6 +93,21 @@ def _ncn(gen, sd, peaky):
     sd["ncn.conv.2.bias"] = 0.01 * torch.randn(1, generator=gen)
 
 
+def make_ncn_state_dict(seed, kernel_sizes, channels, gain=1.0, bias=0.01, prefix="ncn."):
+    """Seeded NeighConsensus(kernel_sizes, channels) tensors in the stored layout [k, c_out, c_in, k, k, k]
+    (conv4d.py:119-120) under the keys `prefix`conv.{2i}.weight / .bias: Xavier-uniform filters as the reference
+    initialises them (networks/modules.py:154-166) times `gain`, biases `bias` * N(0, 1).  A generator of its own:
+    `make_state_dict` keeps its draws."""
+    gen = torch.Generator().manual_seed(int(seed))
+    sd, cin = {}, 1
+    for i, (k, c) in enumerate(zip(kernel_sizes, channels)):
+        w = _xavier(gen, c, cin, k, k, k, k) * gain
+        sd[f"{prefix}conv.{2 * i}.weight"] = w.permute(2, 0, 1, 3, 4, 5).contiguous()
+        sd[f"{prefix}conv.{2 * i}.bias"] = bias * torch.randn(c, generator=gen)
+        cin = c
+    return sd
+
+
 def _regressor(gen, sd, prefix, feat_dim=259, regressor_config=None):
     """One FeatRegressNet (networks/modules.py:56-112) of `regressor_config` (None: the released one) on `feat_dim`
     channels per image.  The draws of the released configuration come in the order they always had."""
