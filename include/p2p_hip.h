@@ -387,6 +387,48 @@ int p2p_nhwc_to_nchw(const float *x, int n, int h, int w, int c, float *y, p2p_s
 /* out[i] = float bits of max |x| over the count values of item i (items are count values apart).                 */
 int p2p_absmax_batch(const float *x, size_t count, int items, int *out, p2p_stream_t stream);
 
+/* ---- image preprocessing (since version 107) --------------------------------------------------- */
+
+/* Pillow's Image.resize(size, Image.BICUBIC) for 8-bit RGB (default box, no reducing_gap), BIT FOR BIT, optionally fused with
+ * the /255, -mean, /std normalisation -- reference utils/datasets/preprocess.py:32-60 (load_im_flexible) from the decoded
+ * pixels on.  csrc/preprocess.hip: a horizontal pass into a uint8 intermediate image, then a vertical pass, in Pillow's
+ * fixed-point arithmetic (coefficients with 22 fractional bits, int32 accumulator starting at 2^21, clip8(acc >> 22)).
+ *
+ * The library computes no coefficient: per axis whose size changes the caller provides a TABLE in DEVICE memory, int32,
+ *   bounds [out][2]      (first input coordinate, number of taps n <= ksize) per output coordinate, then
+ *   coeffs [out][ksize]  the n fixed-point coefficients of that coordinate, zero beyond n,
+ * with ksize = (int)ceil(2 * max(in / out, 1)) * 2 + 1 in double arithmetic, computed on the host the way Pillow's
+ * precompute_coeffs + normalize_coeffs_8bpc do (patch2pix_amd.utils.datasets.preprocess.resize_tables is that computation;
+ * the Python layer uploads the tables through its ring of pinned buffers).  One table serves every item of that (in, out)
+ * pair.  An axis that keeps its size has a NULL table and is copied.  ksize_x / ksize_y are checked against the sizes
+ * (P2P_EINVAL); windows are clamped to the image on the device, so a malformed table gives wrong pixels, never a fault.
+ * With Pillow's tables the first window starts at 0 and the last one ends at `in`: the horizontal pass covers all in_h rows,
+ * which are exactly the rows the vertical pass reads.
+ *
+ *   items      HOST array of `batch` descriptors: pixels = DEVICE pointer to uint8 [in_h, in_w, 3]; every item its own size
+ *   out_u8     optional, device: uint8 [batch, out_h, out_w, 3]
+ *   out_f32    optional, device: item i is written as float32 [3, out_h, out_w] at out_f32 + i * out_f32_stride (floats;
+ *              >= 3 out_h out_w -- a slot range of a larger [B,3,H,W] tensor), value lut[c * 256 + byte]; lut: device
+ *              float32 [3,256], required with out_f32.  At least one of the two outputs.
+ *   workspace  p2p_resize_workspace_bytes(batch, largest in_h, largest in_w, out_h, out_w) bytes of device memory, 16-byte
+ *              aligned: the intermediate images (in_h rows of out_w pixels at a 16-byte pitch per item).  It does NOT hold the
+ *              tables (they are the caller's, see above).  May be NULL when no item changes its width.
+ * Limits: every side 1..16384; a width ratio in_w / out_w up to 2048 (P2P_EUNSUPPORTED beyond: the taps of one output pixel
+ * and the input segment they read are staged in 64 KiB of LDS) -- this covers every input side up to 8192 with every output
+ * side from 4 up, above the input side (upscaling) included.  Null pointers and sizes <= 0 -> P2P_EINVAL, a workspace that is
+ * missing or too small -> P2P_ENOMEM, both before the device is touched.  Nothing is allocated; two launches per 64 items,
+ * asynchronous on `stream`.  The query returns 0 for bad arguments.                                                    */
+typedef struct p2p_resize_item {
+    const uint8_t *pixels;
+    int in_h, in_w;
+    const int32_t *table_x, *table_y;      /* in_w -> out_w, in_h -> out_h; NULL where the size stays */
+    int ksize_x, ksize_y;                  /* ignored for a NULL table */
+} p2p_resize_item;
+size_t p2p_resize_workspace_bytes(int batch, int max_in_h, int max_in_w, int out_h, int out_w);
+int p2p_resize_bicubic_batch(const p2p_resize_item *items, int batch, int out_h, int out_w, uint8_t *out_u8, float *out_f32,
+                             size_t out_f32_stride, const float *lut, void *workspace, size_t workspace_bytes,
+                             p2p_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,11 @@ class NcnTensors(ctypes.Structure):
     _fields_ = [("w", ctypes.c_void_p * 4), ("b", ctypes.c_void_p * 4)]
 
 
+class ResizeItem(ctypes.Structure):
+    _fields_ = [("pixels", ctypes.c_void_p), ("in_h", ctypes.c_int), ("in_w", ctypes.c_int),
+                ("table_x", ctypes.c_void_p), ("table_y", ctypes.c_void_p), ("ksize_x", ctypes.c_int), ("ksize_y", ctypes.c_int)]
+
+
 class Pyramid(ctypes.Structure):
     _fields_ = [("level", ctypes.c_void_p * 4), ("height", ctypes.c_int), ("width", ctypes.c_int)]
 
@@ -154,6 +159,12 @@ p2p_maxpool_nhwc = _sig("p2p_maxpool_nhwc", ctypes.c_int, [ctypes.c_void_p] + [c
 p2p_nhwc_to_nchw = _sig("p2p_nhwc_to_nchw", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p, c_stream])
 p2p_absmax_batch = _sig("p2p_absmax_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p, c_stream])
 
+p2p_resize_workspace_bytes = _sig("p2p_resize_workspace_bytes", ctypes.c_size_t, [ctypes.c_int] * 5)
+p2p_resize_bicubic_batch = _sig("p2p_resize_bicubic_batch", ctypes.c_int,
+                                [ctypes.POINTER(ResizeItem)] + [ctypes.c_int] * 3 +
+                                [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                 c_stream])
+
 p2p_regressor_set_mode = _sig("p2p_regressor_set_mode", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int])
 p2p_regressor_get_mode = _sig("p2p_regressor_get_mode", ctypes.c_int, [ctypes.c_void_p])
 REGRESS_MODES = {"f32": 0, "fp16x2": 3, "fp16x2w": 4}
@@ -166,7 +177,7 @@ EXPORTS = ["p2p_version", "p2p_last_error", "p2p_ncn_create", "p2p_ncn_destroy",
            "p2p_regressor_get_mode", "p2p_conv_create", "p2p_conv_destroy", "p2p_conv_set_tile", "p2p_conv_forward", "p2p_absmax_batch", "p2p_stem_create", "p2p_stem_destroy", "p2p_stem_forward",
            "p2p_maxpool_nhwc", "p2p_nhwc_to_nchw", "p2p_regressor_create_config", "p2p_regress_workspace_bytes_for",
            "p2p_coarse_matches_topk_batch", "p2p_ncn_create_config", "p2p_ncn_is_generic", "p2p_coarse_workspace_bytes_for",
-           "p2p_neigh_consensus_workspace_bytes"]
+           "p2p_neigh_consensus_workspace_bytes", "p2p_resize_workspace_bytes", "p2p_resize_bicubic_batch"]
 
 
 def check(status, what):

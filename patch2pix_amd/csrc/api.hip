@@ -14,10 +14,11 @@ void set_error(const char *fmt, ...) {
 }  // namespace p2p
 
 #ifdef P2P_EXPERIMENT
-extern "C" int p2p_version(void) { return 106 | P2P_VERSION_EXPERIMENT; }
+extern "C" int p2p_version(void) { return 107 | P2P_VERSION_EXPERIMENT; }
 #else
-extern "C" int p2p_version(void) { return 106; }
+extern "C" int p2p_version(void) { return 107; }
 #endif
 extern "C" const char *p2p_last_error(void) { return p2p::g_err; }
 
 #include "regress_api.hip"
+#include "preprocess.hip"       // bicubic resize + normalisation (kernels and their entry points; no unit of its own)

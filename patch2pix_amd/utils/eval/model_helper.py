@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from ..common.setup_helper import load_weights
-from ..datasets.preprocess import load_im_flexible, load_im_pixels, load_im_tensor, normalise_pixels
+from ..datasets.preprocess import (decode_pixels, load_im_flexible, load_im_pixels, load_im_tensor, normalise_pixels,
+                                   resize_pixels_device, upload_pixels)
 from ...networks.patch2pix import Patch2Pix
 from ... import ops
 
@@ -108,6 +109,21 @@ def _load_pair(net, im1, im2, ksize, imsize):
     return tensors[0], tensors[1], np.array([factors])
 
 
+def _load_pair_device(net, im1, im2, ksize, imsize):
+    """`_load_pair` with only the decoding on the host: the original pixels of both images go up in one copy and are
+    resized (Pillow's bicubic, bit for bit) and normalised on the device."""
+    global _decoders
+    if _decoders is None:
+        from concurrent.futures import ThreadPoolExecutor
+        _decoders = ThreadPoolExecutor(max_workers=2, thread_name_prefix="p2p-decode")
+    second = _decoders.submit(decode_pixels, im2, ksize, net.upsample, imsize=imsize)
+    decoded = [decode_pixels(im1, ksize, net.upsample, imsize=imsize), None]
+    decoded[1] = second.result()
+    pixels = upload_pixels([d[0] for d in decoded], net.device)
+    tensors = [resize_pixels_device(p, d[1], normalise=True) for p, d in zip(pixels, decoded)]
+    return tensors[0], tensors[1], np.array([tuple(decoded[0][2]) + tuple(decoded[1][2])])
+
+
 def _host(t):
     return t.detach().cpu().numpy()
 
@@ -136,11 +152,15 @@ def estimate_matches(net, im1, im2, ksize=2, ncn_thres=0.0, mutual=True, io_thre
     return to_original * refined, confidence, to_original * proposals
 
 
-def estimate_matches_device(net, im1, im2, ksize=2, ncn_thres=0.0, mutual=True, io_thres=0.25, imsize=None):
+def estimate_matches_device(net, im1, im2, ksize=2, ncn_thres=0.0, mutual=True, io_thres=0.25, imsize=None, resize="host"):
     """estimate_matches(eval_type='fine') with NOTHING between the image tensors and the result on the host
     (non-reference entry point): coarse stage, filter_coarse, both regressors and the io_thres / scaling tail of
-    model_helper.py:92-109 all run on the device; one device-to-host copy at the end.  Same return triple."""
-    t1, t2, to_original = _load_pair(net, im1, im2, ksize, imsize)
+    model_helper.py:92-109 all run on the device; one device-to-host copy at the end.  Same return triple.
+    resize="device": the bicubic resize runs on the device as well (csrc/preprocess.hip, equal to Pillow's bit for bit); the
+    host only decodes."""
+    if resize not in ("host", "device"):
+        raise ValueError(f"resize must be 'host' or 'device', got {resize!r}")
+    t1, t2, to_original = (_load_pair_device if resize == "device" else _load_pair)(net, im1, im2, ksize, imsize)
     with torch.no_grad():
         fine, scores, coarse, counts = net.predict_fine_device(net.extract.pyramid(t1), net.extract.pyramid(t2), ksize=ksize,
                                                                ncn_thres=ncn_thres, mutual=mutual)

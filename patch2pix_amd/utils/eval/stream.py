@@ -19,11 +19,24 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from ..datasets.preprocess import load_im_pixels, normalise_pixels
+from ..datasets.preprocess import decode_pixels, load_im_pixels, normalise_pixels, resize_pixels_device, upload_pixels
+
+
+class _Decoded:
+    """A decoded image that is resized on the device: the original pixels, and as `shape` the [H,W,3] it will have (what
+    batches are grouped by)."""
+    __slots__ = ("pixels", "shape")
+
+    def __init__(self, pixels, out_hw):
+        self.pixels, self.shape = pixels, (out_hw[0], out_hw[1], 3)
 
 
 def _load(job):
-    idx, im1, im2, ksize, upsample, imsize = job
+    idx, im1, im2, ksize, upsample, imsize = job[:6]
+    if len(job) > 6 and job[6] == "device":                                   # decode only
+        a1, hw1, s1 = decode_pixels(im1, ksize, upsample, imsize=imsize)
+        a2, hw2, s2 = decode_pixels(im2, ksize, upsample, imsize=imsize)
+        return idx, _Decoded(a1, hw1), _Decoded(a2, hw2), np.array([tuple(s1) + tuple(s2)]), job
     t1, s1 = load_im_pixels(im1, ksize, upsample, imsize=imsize)          # uint8 [H,W,3]: normalised on the device
     t2, s2 = load_im_pixels(im2, ksize, upsample, imsize=imsize)
     return idx, t1, t2, np.array([tuple(s1) + tuple(s2)]), job
@@ -55,6 +68,19 @@ def _upload(tensors, device):
     slot[1] = torch.cuda.Event(blocking=True)
     slot[1].record(torch.cuda.current_stream(device))
     return normalise_pixels(dev)
+
+
+def _upload_resize(first, second, device):
+    """resize="device": the original pixels of both images of every pair in one pinned buffer and one copy, then one resize
+    + normalise call per output size on the consuming stream -> (im1, im2, both); `both` is the [2B,3,H,W] tensor the two
+    are halves of when the sizes agree (else None)."""
+    pixels = upload_pixels([d.pixels for d in first + second], device)
+    n = len(first)
+    if first[0].shape == second[0].shape:
+        both = resize_pixels_device(pixels, first[0].shape[:2], normalise=True)
+        return both[:n], both[n:], both
+    return (resize_pixels_device(pixels[:n], first[0].shape[:2], normalise=True),
+            resize_pixels_device(pixels[n:], second[0].shape[:2], normalise=True), None)
 
 
 _out_pool = {}      # device -> {"slots": [[pinned [cap, 9] tensor, event-or-None], ...], "turn": int}: staging of the match arrays
@@ -168,15 +194,21 @@ def _bounded_map(pool, fn, jobs, ahead):
 
 
 def estimate_matches_stream(net, pairs, ksize=2, ncn_thres=0.0, mutual=True, io_thres=0.25, imsize=None,
-                            batch=8, workers=4, lookahead=None, device_filter=True):
+                            batch=8, workers=4, lookahead=None, device_filter=True, resize="host"):
     """Generator over `pairs` (iterable of (im1, im2) paths / file objects): yields
     (matches float64 [M,4], scores float32 [M], coarse_matches float64 [M,4]) per pair, in order.
     workers: loader threads (a 480x640 JPEG pair decodes in 2 ms: a few threads feed the GPU); lookahead: pairs decoded
     ahead of the batch being matched (default 3 batches); device_filter=False keeps filter_coarse on the host (the
-    reference's numpy semantics literally; same results, tests/test_gpu_parity.py)."""
+    reference's numpy semantics literally; same results, tests/test_gpu_parity.py); resize="device": the loader threads
+    only decode, the bicubic resize (Pillow's, bit for bit: csrc/preprocess.hip) and the normalisation of a whole batch are
+    one call on the device -- same results (tests/test_gpu_resize.py)."""
+    if resize not in ("host", "device"):
+        raise ValueError(f"resize must be 'host' or 'device', got {resize!r}")
+    if resize == "device" and torch.device(net.device).type != "cuda":
+        raise ValueError("resize='device' needs the network on a GPU")
     on_device = (device_filter and torch.device(net.device).type == "cuda" and getattr(net, "panc", 1) == 1
                  and hasattr(net, "predict_fine_device"))
-    jobs = ((i, a, b, ksize, net.upsample, imsize) for i, (a, b) in enumerate(pairs))
+    jobs = ((i, a, b, ksize, net.upsample, imsize, resize) for i, (a, b) in enumerate(pairs))
     pending = deque()          # (ticket, metas) whose fine stage has not been issued yet
     issued = deque()           # batches whose fine stage is enqueued and whose results are being copied to the host
     with ThreadPoolExecutor(max_workers=max(1, workers)) as pool, torch.no_grad():
@@ -190,10 +222,14 @@ def estimate_matches_stream(net, pairs, ksize=2, ncn_thres=0.0, mutual=True, io_
             """Backbone on the 2*B images of the current group, coarse stage enqueued, ticket queued."""
             if not group:
                 return
-            im1 = _upload([g[1] for g in group], net.device)
-            im2 = _upload([g[2] for g in group], net.device)
+            both = None
+            if resize == "device":
+                im1, im2, both = _upload_resize([g[1] for g in group], [g[2] for g in group], net.device)
+            else:
+                im1 = _upload([g[1] for g in group], net.device)
+                im2 = _upload([g[2] for g in group], net.device)
             if im1.shape == im2.shape:
-                feats = net.extract.pyramid(torch.cat([im1, im2]))
+                feats = net.extract.pyramid(both if both is not None else torch.cat([im1, im2]))
                 n = im1.shape[0]
                 f1, f2 = [f[:n] for f in feats], [f[n:] for f in feats]
             else:
