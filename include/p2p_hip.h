@@ -244,7 +244,7 @@ int p2p_coarse_matches_batch(const float *corr4d, const uint8_t *delta, int batc
  * score -inf (do_softmax = 0) or 0 (do_softmax = 1; NaN if no value is above -inf).  Softmax scores are expf(x_t - max) / sum expf(x - max) with the sum taken exactly as those functions
  * take it: topk = 1 with do_softmax = 1 gives their matches and scores bit for bit.
  * 1 <= topk <= 8 and topk <= min(nA, nB) (torch.topk raises beyond that as well), else P2P_EINVAL; every other argument as
- * in the batch form above.  One pass over the volume per rank (csrc/coarse.hip, section 5).                        */
+ * in the batch form above.  One pass over the volume per rank (csrc/matches.hip).                        */
 int p2p_coarse_matches_topk_batch(const float *corr4d, const uint8_t *delta, int batch, int hA, int wA, int hB, int wB,
                                   int ksize, int upsample, int center, int topk, int do_softmax,
                                   int64_t *matches_out, float *scores_out, p2p_stream_t stream);

@@ -20,5 +20,6 @@ extern "C" int p2p_version(void) { return 107; }
 #endif
 extern "C" const char *p2p_last_error(void) { return p2p::g_err; }
 
-#include "regress_api.hip"
+#include "coarse_api.hip"        // coarse stage: handle, workspace, entry points
+#include "regress_api.hip"       // fine stage: handle, modes, entry points
 #include "preprocess.hip"       // bicubic resize + normalisation (kernels and their entry points; no unit of its own)

@@ -21,12 +21,10 @@
 // kernel takes the pair from blockIdx.z and a per-pair stride for each of its pointers, so a batch is
 // ONE launch per kernel (B x the work-groups: the 30x40x30x40 volume of a single 480x640 pair does not
 // fill 256 CUs in the consensus layers).
-#include "p2p_common.h"
-
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+//
+// This file: sections 1-3, each kernel with its launcher.  4, the neighbourhood consensus (ncn/model.py:145-155; conv4d.py:12-74):
+// consensus.hip (the released stack, one fused kernel) and consensus_generic.hip (any other); 5, matches.hip; host API: coarse_api.hip.
+#include "coarse_common.h"
 
 namespace p2p {
 
@@ -53,17 +51,6 @@ constexpr float CORR_FP16_SCALE = 4096.0f;
 // every block of 32 (= two cells) so that cell e of the block sits on the rows (q & 3) + 8 (q >> 2) + 4 e, q = di * 4 + dj:
 // the rows whose products one half e of a wave holds in its 32x32 accumulator block, in register order (corr_pool_kernel<4>).
 __device__ __forceinline__ int prep_row_k4(int pp) { return (pp & ~31) + (pp & 3) + 2 * (pp & 12) + ((pp >> 2) & 4); }
-struct PrepArgs {
-    const float *F[2];
-    unsigned short *Fn[2];
-    int h[2], w[2];
-    size_t sF[2];
-    int C, k;
-    size_t sFn;
-    int *keys;
-    int nkeys;
-    size_t sKeys;
-};
 // (PERM_A = the k = 4 instantiation: a template parameter, so that the kernel of k = 1, 2 is the code it was without it)
 template <bool PERM_A>
 __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
@@ -139,6 +126,12 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
             d[128 * 32] = __builtin_bit_cast(unsigned short, (_Float16)(x - (float)h0));
         }
     }
+}
+
+void launch_prep(const PrepArgs &a, unsigned nz, hipStream_t stream) {
+    const int gp = std::max(ceil_div(std::max(a.h[0] * a.w[0], a.h[1] * a.w[1]), PREP_P), ceil_div(a.nkeys + 1, 256));
+    if (a.k == 4) hipLaunchKernelGGL(prep_kernel<true>, dim3(gp, 2, nz), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(prep_kernel<false>, dim3(gp, 2, nz), dim3(256), 0, stream, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -421,6 +414,28 @@ __global__ __launch_bounds__(256, 2) void corr_pool_kernel(const unsigned short 
   }
 }
 
+int launch_corr_pool(const unsigned short *fnA, const unsigned short *fnB, int nA, int nB, int C, int ksize, float *P, uint8_t *delta,
+                     size_t sAB, size_t sP, size_t sDelta, unsigned nz, hipStream_t stream) {
+    int dev = 0;
+    P2P_HIP_CHECK(hipGetDevice(&dev));
+    static DeviceOnce attr_set_dev;      // per device: a process may drive several GPUs
+    if (!attr_set_dev.done(dev)) {
+        for (const void *kernel : {(const void *)corr_pool_kernel<1>, (const void *)corr_pool_kernel<2>, (const void *)corr_pool_kernel<4>})
+            P2P_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CX_LDS));
+        attr_set_dev.set(dev);
+    }
+    const int gx = ceil_div(nB, CT), gy = ceil_div(nA, CT);
+    const long long ntiles = (long long)gx * gy * nz;
+    P2P_REQUIRE(ntiles < (1ll << 30), P2P_EUNSUPPORTED, "p2p_coarse_forward: %lld correlation tiles in one launch", ntiles);
+    // persistent work-groups: two fit a compute unit, 32 compute units per XCD
+    const int per_xcd = (int)((ntiles + 7) / 8);
+    const dim3 cgrid((unsigned)(8 * std::min(per_xcd, 64)));
+    if (ksize == 1) delta = nullptr, sDelta = 0;       // nothing was pooled: no argmax to record
+    const auto kernel = ksize == 1 ? corr_pool_kernel<1> : (ksize == 4 ? corr_pool_kernel<4> : corr_pool_kernel<2>);
+    hipLaunchKernelGGL(kernel, cgrid, dim3(256), CX_LDS, stream, fnA, fnB, nA, nB, C, P, delta, sAB, sP, sDelta, gx, gy, (int)ntiles, per_xcd);
+    return P2P_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // 3. row / column maxima of an [nA][nB] matrix (the two torch.max of ncn/model.py:165-166)
 // ------------------------------------------------------------------------------------------------
@@ -462,6 +477,13 @@ __global__ __launch_bounds__(256) void maxima_kernel(const float *__restrict__ X
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) rm = fmaxf(rm, __shfl_xor(rm, m));
     if (lane == 0) rkey[row] = f2key(rm);
+}
+
+void launch_maxima(const float *X, int nA, int nB, int *rkey, int *ckey, size_t sX, size_t sKeys, const float *X2, unsigned nz,
+                   hipStream_t stream) {
+    const int col_groups = ceil_div(nB, 256) * ceil_div(nA, 64);
+    const dim3 grid(col_groups + ceil_div(nA, 4), 1, nz);
+    hipLaunchKernelGGL(maxima_kernel, grid, dim3(256), 0, stream, X, nA, nB, rkey, ckey, sX, sKeys, X2, col_groups);
 }
 
 // MutualMatching value (ncn/model.py:168-175): x * ((x / (max_over_B + eps)) * (x / (max_over_A + eps)))
@@ -522,8 +544,8 @@ __global__ __launch_bounds__(256) void mm_apply_kernel(const float *X, int nA, i
     }
 }
 
-static void launch_mm_apply(const float *X, int nA, int nB, const int *rkey, const int *ckey, float *out, size_t sX,
-                            size_t sKeys, size_t sOut, int *amax, const float *X2, size_t nz, hipStream_t stream) {
+void launch_mm_apply(const float *X, int nA, int nB, const int *rkey, const int *ckey, float *out, size_t sX, size_t sKeys,
+                     size_t sOut, int *amax, const float *X2, size_t nz, hipStream_t stream) {
     const bool vec = nB % 4 == 0 && sX % 4 == 0 && sOut % 4 == 0 && sKeys % 4 == 0 && ((uintptr_t)X & 15) == 0 &&
                      ((uintptr_t)out & 15) == 0 && ((uintptr_t)X2 & 15) == 0 && ((uintptr_t)ckey & 15) == 0;
     const size_t items = (size_t)nA * (nB / (vec ? 4 : 1));
@@ -532,517 +554,8 @@ static void launch_mm_apply(const float *X, int nA, int nB, const int *rkey, con
     else hipLaunchKernelGGL(mm_apply_kernel<false>, grid, dim3(256), 0, stream, X, nA, nB, rkey, ckey, out, sX, sKeys, sOut, amax, X2);
 }
 
-// ------------------------------------------------------------------------------------------------
-// 4. neighbourhood consensus (ncn/model.py:145-155; conv4d.py:12-74): consensus.hip, one fused kernel for every
-//    volume and batch size (the released stack); consensus_generic.hip, one launch per layer and branch (any other stack)
-// ------------------------------------------------------------------------------------------------
-}  // namespace p2p
-#include "consensus_generic.hip"      // the shape-generic layers and their handle (no unit of its own)
-namespace p2p {
-// ------------------------------------------------------------------------------------------------
-// 5. matches (ncn/extract_ncmatches.py:6-94 twice; patch2pix.py:340-375) and their top-k form (:96-158)
-// ------------------------------------------------------------------------------------------------
-struct MatchArgs {
-    const float *X;
-    const uint8_t *delta;
-    int hA, wA, hB, wB, ksize, upsample, center;
-    long long *matches;
-    float *scores;
-    size_t sX, sM;      // per-pair strides: cells of the volume, rows of the match list
-};
-__device__ __forceinline__ MatchArgs match_args_of_pair(MatchArgs m, size_t z) {
-    m.X += z * m.sX;
-    if (m.delta) m.delta += z * m.sX;
-    m.matches += z * m.sM * 4;
-    m.scores += z * m.sM;
-    return m;
-}
-
-// one match row: cell (ra, cb) relocalised and scaled to pixels; `s` is the softmax denominator of the row's maximum
-// (RECIP) or the score itself (the top-k kernels)
-template <bool RECIP>
-__device__ __forceinline__ void emit_match_as(const MatchArgs &m, int out_row, int ra, int cb, float s) {
-    int ia = ra / m.wA, ja = ra - ia * m.wA, ib = cb / m.wB, jb = cb - ib * m.wB;
-    if (m.ksize > 1 && m.delta) {
-        const int k = m.ksize;
-        int s = m.delta[(size_t)ra * (m.hB * m.wB) + cb];
-        const int dl = s % k; s /= k;
-        const int dk = s % k; s /= k;
-        const int dj = s % k; s /= k;
-        ia = ia * k + s; ja = ja * k + dj; ib = ib * k + dk; jb = jb * k + dl;
-    } else if (m.ksize > 1) {
-        ia *= m.ksize; ja *= m.ksize; ib *= m.ksize; jb *= m.ksize;
-    }
-    const long long up = m.upsample, off = m.center ? m.upsample / 2 : 0;
-    long long *o = m.matches + (size_t)out_row * 4;
-    o[0] = up * ja + off; o[1] = up * ia + off; o[2] = up * jb + off; o[3] = up * ib + off;
-    m.scores[out_row] = RECIP ? 1.0f / s : s;       // max of softmax = exp(0) / sum exp(x - max)
-}
-__device__ __forceinline__ void emit_match(const MatchArgs &m, int out_row, int ra, int cb, float sum_exp) {
-    emit_match_as<true>(m, out_row, ra, cb, sum_exp);
-}
-
-// direction B->A: one block per 16 columns (a row of the block = half a 128-byte line: 8-column blocks fetched every line of
-// the volume four times; 32 columns leave too few blocks per pair), 16 interleaved row slices
-constexpr int MC_COLS = 16, MC_SLICES = 16;
-__global__ __launch_bounds__(256) void match_cols_kernel(MatchArgs m_) {
-    const MatchArgs m = match_args_of_pair(m_, blockIdx.z);
-    __shared__ float smax[MC_SLICES][MC_COLS];
-    __shared__ int sarg[MC_SLICES][MC_COLS];
-    __shared__ float ssum[MC_SLICES][MC_COLS];
-    const int nA = m.hA * m.wA, nB = m.hB * m.wB;
-    const int cs = threadIdx.x & (MC_COLS - 1), rs = threadIdx.x / MC_COLS;
-    const int col = blockIdx.x * MC_COLS + cs;
-    const bool ok = col < nB;
-    float best = -INFINITY;
-    int arg = 0x7fffffff;
-    if (ok)
-        for (int r = rs; r < nA; r += MC_SLICES) {
-            const float v = m.X[(size_t)r * nB + col];
-            if (v > best) { best = v; arg = r; }
-        }
-    smax[rs][cs] = best; sarg[rs][cs] = arg;
-    __syncthreads();
-    float gb = smax[0][cs];
-    int ga = sarg[0][cs];
-#pragma unroll
-    for (int s = 1; s < MC_SLICES; ++s) {
-        const float v = smax[s][cs];
-        const int a = sarg[s][cs];
-        if (v > gb || (v == gb && a < ga)) { gb = v; ga = a; }
-    }
-    float sum = 0.f;
-    if (ok)
-        for (int r = rs; r < nA; r += MC_SLICES) sum += expf(m.X[(size_t)r * nB + col] - gb);
-    ssum[rs][cs] = sum;
-    __syncthreads();
-    if (rs == 0 && ok) {
-        float t = 0.f;
-#pragma unroll
-        for (int s = 0; s < MC_SLICES; ++s) t += ssum[s][cs];
-        emit_match(m, col, ga, col, t);
-    }
-}
-
-// direction A->B: one wave per row
-__global__ __launch_bounds__(256) void match_rows_kernel(MatchArgs m_) {
-    const MatchArgs m = match_args_of_pair(m_, blockIdx.z);
-    const int nA = m.hA * m.wA, nB = m.hB * m.wB;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= nA) return;
-    const float *x = m.X + (size_t)row * nB;
-    float best = -INFINITY;
-    int arg = 0x7fffffff;
-    for (int c = lane; c < nB; c += 64) {
-        const float v = x[c];
-        if (v > best) { best = v; arg = c; }
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const float ov = __shfl_xor(best, s);
-        const int oa = __shfl_xor(arg, s);
-        if (ov > best || (ov == best && oa < arg)) { best = ov; arg = oa; }
-    }
-    float sum = 0.f;
-    for (int c = lane; c < nB; c += 64) sum += expf(x[c] - best);
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) sum += __shfl_xor(sum, s);
-    if (lane == 0) emit_match(m, nB + row, row, arg, sum);
-}
-
-// The topk best cells per cell and direction (corr_to_matches_topk, extract_ncmatches.py:96-158), ordered by descending
-// value and, among equal values, ascending index.  No candidate list is kept (indexed at run time it would live in
-// scratch): rank t is the arg-max over the cells that come strictly AFTER rank t-1's (value, index) in that order, found
-// by one more pass of the reduction of the kernels above over a volume that sits in L2 / Infinity Cache.  topk passes, plus
-// the softmax sum after rank 0 -- the same slices and the same tree as above, so rank 0 of topk = 1 is their output bit for
-// bit.  do_softmax = 0: the score is the value itself.
-__device__ __forceinline__ bool topk_after(float v, int i, float pv, int pi) { return v < pv || (v == pv && i > pi); }
-
-// direction B->A, rank t of column c -> row t*nB + c (the reference's view(batch, topk, -1))
-__global__ __launch_bounds__(256) void match_cols_topk_kernel(MatchArgs m_, int topk, int do_softmax) {
-    const MatchArgs m = match_args_of_pair(m_, blockIdx.z);
-    __shared__ float smax[MC_SLICES][MC_COLS];
-    __shared__ int sarg[MC_SLICES][MC_COLS];
-    __shared__ float ssum[MC_SLICES][MC_COLS];
-    const int nA = m.hA * m.wA, nB = m.hB * m.wB;
-    const int cs = threadIdx.x & (MC_COLS - 1), rs = threadIdx.x / MC_COLS;
-    const int col = blockIdx.x * MC_COLS + cs;
-    const bool ok = col < nB;
-    float pv = INFINITY, top = 0.f, total = 1.f;     // previous rank's value (everything comes after +inf, -1), rank 0's, sum exp
-    int pi = -1;
-    for (int t = 0; t < topk; ++t) {
-        float best = -INFINITY;
-        int arg = 0x7fffffff;
-        if (ok)
-            for (int r = rs; r < nA; r += MC_SLICES) {
-                const float v = m.X[(size_t)r * nB + col];
-                if (topk_after(v, r, pv, pi) && v > best) { best = v; arg = r; }
-            }
-        smax[rs][cs] = best; sarg[rs][cs] = arg;
-        __syncthreads();
-        float gb = smax[0][cs];
-        int ga = sarg[0][cs];
-#pragma unroll
-        for (int s = 1; s < MC_SLICES; ++s) {
-            const float v = smax[s][cs];
-            const int a = sarg[s][cs];
-            if (v > gb || (v == gb && a < ga)) { gb = v; ga = a; }
-        }
-        if (t == 0) {
-            top = gb;
-            if (do_softmax) {
-                float sum = 0.f;
-                if (ok)
-                    for (int r = rs; r < nA; r += MC_SLICES) sum += expf(m.X[(size_t)r * nB + col] - gb);
-                ssum[rs][cs] = sum;
-                __syncthreads();
-                if (rs == 0) {
-                    total = 0.f;
-#pragma unroll
-                    for (int s = 0; s < MC_SLICES; ++s) total += ssum[s][cs];
-                }
-            }
-        }
-        // topk <= nA finite values always leave a candidate; a volume of NaN / -inf does not, and must not index past the delta
-        ga = min(ga, nA - 1);
-        if (rs == 0 && ok)
-            emit_match_as<false>(m, t * nB + col, ga, col, do_softmax ? (t == 0 ? 1.0f : expf(gb - top)) / total : gb);
-        pv = gb; pi = ga;
-        __syncthreads();        // the next rank overwrites smax / sarg
-    }
-}
-
-// direction A->B, rank t of row r -> row topk*nB + r*topk + t (view(batch, -1, topk), after the whole B->A list): one wave per row
-__global__ __launch_bounds__(256) void match_rows_topk_kernel(MatchArgs m_, int topk, int do_softmax) {
-    const MatchArgs m = match_args_of_pair(m_, blockIdx.z);
-    const int nA = m.hA * m.wA, nB = m.hB * m.wB;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= nA) return;
-    const float *x = m.X + (size_t)row * nB;
-    float pv = INFINITY, top = 0.f, total = 1.f;
-    int pi = -1;
-    for (int t = 0; t < topk; ++t) {
-        float best = -INFINITY;
-        int arg = 0x7fffffff;
-        for (int c = lane; c < nB; c += 64) {
-            const float v = x[c];
-            if (topk_after(v, c, pv, pi) && v > best) { best = v; arg = c; }
-        }
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) {
-            const float ov = __shfl_xor(best, s);
-            const int oa = __shfl_xor(arg, s);
-            if (ov > best || (ov == best && oa < arg)) { best = ov; arg = oa; }
-        }
-        if (t == 0) {
-            top = best;
-            if (do_softmax) {
-                float sum = 0.f;
-                for (int c = lane; c < nB; c += 64) sum += expf(x[c] - best);
-#pragma unroll
-                for (int s = 32; s >= 1; s >>= 1) sum += __shfl_xor(sum, s);
-                total = sum;
-            }
-        }
-        arg = min(arg, nB - 1);
-        if (lane == 0)
-            emit_match_as<false>(m, topk * nB + row * topk + t, row, arg, do_softmax ? (t == 0 ? 1.0f : expf(best - top)) / total : best);
-        pv = best; pi = arg;
-    }
-}
-
-__global__ void delta_unpack_kernel(const uint8_t *__restrict__ delta, size_t n, int k, long long *__restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int s = delta[i];
-    out[3 * n + i] = s % k; s /= k;
-    out[2 * n + i] = s % k; s /= k;
-    out[1 * n + i] = s % k; s /= k;
-    out[i] = s;
-}
-
-// workspace carve-up shared by the size query and the launcher
-struct CoarseWs {
-    size_t fnA, fnB, P, Y, Y2, keys, act, total;   // byte offsets
-};
-// gen: the generic consensus net whose activation buffers the pair's block holds as well (null: a tuned handle, none)
-static CoarseWs coarse_ws(int C, int hA, int wA, int hB, int wB, int k, const NcGen *gen = nullptr) {
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t nA = (size_t)hA * wA, nB = (size_t)hB * wB;
-    const size_t nAc = nA / (k * k), nBc = nB / (k * k);
-    CoarseWs w;
-    size_t off = 0;
-    w.fnA = off; off += al(((nA + 127) / 128) * 128 * C * 4);      // two fp16 planes in blocks of 128 positions x 32 channels
-    w.fnB = off; off += al(((nB + 127) / 128) * 128 * C * 4);
-    w.P = off; off += al(nAc * nBc * 4);
-    w.Y = off; off += al(nAc * nBc * 4);     // the two branches of the consensus net
-    w.Y2 = off; off += al(nAc * nBc * 4);
-    w.keys = off; off += al((2 * (nAc + nBc) + 1) * 4);      // row / column maxima of both mutual matchings + max |X|
-    w.act = off;
-    if (gen) off += nc_generic_ws_bytes(*gen, nAc * nBc);
-    w.total = off;
-    return w;
-}
-
-// consensus.hip
-void pack_nc_fused(const float *w1, const float *b1, const float *w2, std::vector<unsigned char> &out);
-int launch_nc_fused(const float *X, float *Y, float *Y2, size_t stride, int pairs, int d0, int d1, int d2, int d3,
-                    const unsigned char *w_dev, float b2, const int *xmax, size_t xmax_stride, const int *forced_tile,
-                    hipStream_t stream);
-int launch_absmax(const float *x, size_t n, size_t stride, int pairs, int *out, size_t out_stride, hipStream_t stream);
-
 }  // namespace p2p
 
-using namespace p2p;
-
-extern "C" int p2p_ncn_create(const float *w1, const float *b1, const float *w2, const float *b2, p2p_ncn **out) {
-    P2P_REQUIRE(w1 && b1 && w2 && b2 && out, P2P_EINVAL, "p2p_ncn_create: null argument");
-    // stored layout (conv4d.py:119-120): w1s[da][o][ci=0][db][dc][dd], w2s[da][o=0][ci][db][dc][dd] -> MFMA fragments of
-    // both branches (consensus.hip)
-    std::vector<unsigned char> wf;
-    pack_nc_fused(w1, b1, w2, wf);
-    unsigned char *wfd = nullptr;
-    hipError_t e = hipMalloc(&wfd, wf.size());
-    if (e == hipSuccess) e = hipMemcpy(wfd, wf.data(), wf.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (wfd) (void)hipFree(wfd);
-        set_error("upload of the consensus weights failed: %s", hipGetErrorString(e));
-        return P2P_EHIP;
-    }
-    p2p_ncn *n = new p2p_ncn();
-    n->b2 = b2[0];
-    n->wfused = wfd;
-    n->tile[0] = n->tile[1] = n->tile[2] = 0;
-    n->gen = nullptr;
-    *out = n;
-    return P2P_OK;
-}
-
-extern "C" int p2p_ncn_create_config(const p2p_ncn_config *config, const p2p_ncn_tensors *tensors, p2p_ncn **out) {
-    P2P_REQUIRE(out, P2P_EINVAL, "p2p_ncn_create_config: null argument");
-    NcGen *g = nullptr;
-    const int st = nc_generic_create(config, tensors, &g);      // validates before it touches the device
-    if (st != P2P_OK) return st;
-    p2p_ncn *n = new p2p_ncn();
-    n->b2 = 0.f; n->wfused = nullptr;
-    n->tile[0] = n->tile[1] = n->tile[2] = 0;
-    n->gen = g;
-    *out = n;
-    return P2P_OK;
-}
-
-extern "C" int p2p_ncn_is_generic(const p2p_ncn *ncn) { return ncn ? (ncn->gen ? 1 : 0) : -1; }
-
-extern "C" int p2p_ncn_set_tile(p2p_ncn *ncn, int ta, int tb, int tc) {
-    P2P_REQUIRE(ncn && ta >= 0 && tb >= 0 && tc >= 0, P2P_EINVAL, "p2p_ncn_set_tile: bad argument");
-    P2P_REQUIRE(!ncn->gen, P2P_EUNSUPPORTED, "p2p_ncn_set_tile: a generic consensus handle has no work-group tile to force");
-    // (0, 0, 0) = automatic; (ta, tb, tc) with tb, tc > 0 = forced (ta = 0: only the march length is picked); anything else
-    // would be ignored silently
-    P2P_REQUIRE((tb > 0 && tc > 0) || (ta == 0 && tb == 0 && tc == 0), P2P_EINVAL,
-                "p2p_ncn_set_tile: (%d, %d, %d) is neither (0, 0, 0) nor a tile with tb, tc > 0", ta, tb, tc);
-    ncn->tile[0] = ta; ncn->tile[1] = tb; ncn->tile[2] = tc;
-    return P2P_OK;
-}
-
-extern "C" void p2p_ncn_destroy(p2p_ncn *ncn) {
-    if (!ncn) return;
-    if (ncn->wfused) (void)hipFree(ncn->wfused);
-    nc_generic_destroy(ncn->gen);
-    delete ncn;
-}
-
-extern "C" size_t p2p_coarse_workspace_bytes(int channels, int hA, int wA, int hB, int wB, int ksize) {
-    if (channels <= 0 || hA <= 0 || wA <= 0 || hB <= 0 || wB <= 0 || ksize < 1) return 0;
-    return coarse_ws(channels, hA, wA, hB, wB, ksize).total;
-}
-
-extern "C" size_t p2p_coarse_workspace_bytes_for(const p2p_ncn *ncn, int channels, int hA, int wA, int hB, int wB, int ksize) {
-    if (!ncn || channels <= 0 || hA <= 0 || wA <= 0 || hB <= 0 || wB <= 0 || ksize < 1) return 0;
-    return coarse_ws(channels, hA, wA, hB, wB, ksize, ncn->gen).total;
-}
-
-extern "C" size_t p2p_neigh_consensus_workspace_bytes(const p2p_ncn *ncn, int hA, int wA, int hB, int wB) {
-    if (!ncn || hA <= 0 || wA <= 0 || hB <= 0 || wB <= 0) return 0;
-    return ncn->gen ? nc_generic_ws_bytes(*ncn->gen, (size_t)hA * wA * hB * wB) : sizeof(int);
-}
-
-extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, int batch, int C, int hA, int wA, int hB,
-                                        int wB, int ksize, const p2p_ncn *ncn, float *corr4d_out, uint8_t *delta_out,
-                                        void *workspace, size_t workspace_bytes, p2p_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    P2P_REQUIRE(featA && featB && ncn && corr4d_out && workspace, P2P_EINVAL, "p2p_coarse_forward: null argument");
-    P2P_REQUIRE(batch >= 1 && batch <= 65535, P2P_EINVAL, "p2p_coarse_forward: batch %d out of range", batch);
-    P2P_REQUIRE(ksize == 1 || ksize == 2 || ksize == 4, P2P_EUNSUPPORTED, "p2p_coarse_forward: ksize %d not supported (1, 2 or 4)", ksize);
-    P2P_REQUIRE(C > 0 && C % 32 == 0 && C <= 256, P2P_EUNSUPPORTED, "p2p_coarse_forward: channels %d (multiple of 32, <= 256)", C);
-    P2P_REQUIRE(hA > 0 && wA > 0 && hB > 0 && wB > 0 && hA % ksize == 0 && wA % ksize == 0 && hB % ksize == 0 &&
-                    wB % ksize == 0, P2P_EINVAL, "p2p_coarse_forward: feature map sizes must be positive multiples of ksize");
-    // The handle is dereferenced only after the workspace has passed the size every kind of handle needs: callers probe this
-    // entry point's argument checks with placeholder handles (tests/test_cabi_exports.py::test_batch_argument_errors passes
-    // ncn = 1 with a 64-byte workspace and expects the workspace error, as before generic handles existed).
-    const size_t ws_any = coarse_ws(C, hA, wA, hB, wB, ksize).total;
-    P2P_REQUIRE(workspace_bytes >= ws_any, P2P_ENOMEM, "p2p_coarse_forward: workspace %zu < %zu bytes (one pair)", workspace_bytes, ws_any);
-    const CoarseWs ws = coarse_ws(C, hA, wA, hB, wB, ksize, ncn->gen);
-    P2P_REQUIRE(workspace_bytes >= ws.total, P2P_ENOMEM, "p2p_coarse_forward: workspace %zu < %zu bytes (one pair)", workspace_bytes,
-                ws.total);
-    P2P_REQUIRE(!ncn->gen || ((uintptr_t)workspace & 15) == 0, P2P_EINVAL,
-                "p2p_coarse_forward: the workspace of a generic handle must be 16-byte aligned");
-    const int nA = hA * wA, nB = hB * wB, kk = ksize * ksize;
-    const int nAc = nA / kk, nBc = nB / kk;
-    const size_t nel = (size_t)nAc * nBc;
-    const size_t sWs = ws.total / 4;        // every workspace buffer of pair z sits z * ws.total bytes further on
-    const int per_launch = (int)std::min<size_t>(batch, workspace_bytes / ws.total);   // pairs the workspace holds at once
-    const int d0 = hA / ksize, d1 = wA / ksize, d2 = hB / ksize, d3 = wB / ksize;
-    int dev = 0;
-    P2P_HIP_CHECK(hipGetDevice(&dev));
-    static DeviceOnce attr_set_dev;      // per device: a process may drive several GPUs
-    if (!attr_set_dev.done(dev)) {
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)corr_pool_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, CX_LDS));
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)corr_pool_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, CX_LDS));
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)corr_pool_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, CX_LDS));
-        attr_set_dev.set(dev);
-    }
-
-    for (int z0 = 0; z0 < batch; z0 += per_launch) {
-        const unsigned nz = (unsigned)std::min(per_launch, batch - z0);
-        const float *fA = featA + (size_t)z0 * C * nA, *fB = featB + (size_t)z0 * C * nB;
-        float *out = corr4d_out + (size_t)z0 * nel;
-        uint8_t *dout = delta_out ? delta_out + (size_t)z0 * nel : nullptr;
-        char *base = (char *)workspace;
-        unsigned short *fnA = (unsigned short *)(base + ws.fnA), *fnB = (unsigned short *)(base + ws.fnB);
-        float *P = (float *)(base + ws.P), *Y = (float *)(base + ws.Y), *Y2 = (float *)(base + ws.Y2);
-        int *rkey1 = (int *)(base + ws.keys), *ckey1 = rkey1 + nAc, *rkey2 = ckey1 + nBc, *ckey2 = rkey2 + nAc;
-
-        const int nkeys = 2 * (nAc + nBc);
-        int *xmax = rkey1 + nkeys;
-        {
-            PrepArgs pa;
-            pa.F[0] = fA; pa.F[1] = fB; pa.Fn[0] = fnA; pa.Fn[1] = fnB;
-            pa.h[0] = hA; pa.w[0] = wA; pa.h[1] = hB; pa.w[1] = wB;
-            pa.sF[0] = (size_t)C * nA; pa.sF[1] = (size_t)C * nB;
-            pa.C = C; pa.k = ksize; pa.sFn = 2 * sWs;
-            pa.keys = rkey1; pa.nkeys = nkeys; pa.sKeys = sWs;
-            const int gp = std::max(ceil_div(std::max(nA, nB), PREP_P), ceil_div(nkeys + 1, 256));
-            if (ksize == 4) hipLaunchKernelGGL(prep_kernel<true>, dim3(gp, 2, nz), dim3(256), 0, stream, pa);
-            else hipLaunchKernelGGL(prep_kernel<false>, dim3(gp, 2, nz), dim3(256), 0, stream, pa);
-        }
-        {
-            const int gx = ceil_div(nB, CT), gy = ceil_div(nA, CT);
-            const long long ntiles = (long long)gx * gy * nz;
-            P2P_REQUIRE(ntiles < (1ll << 30), P2P_EUNSUPPORTED, "p2p_coarse_forward: %lld correlation tiles in one launch", ntiles);
-            // persistent work-groups: two fit a compute unit, 32 compute units per XCD
-            const int per_xcd = (int)((ntiles + 7) / 8);
-            const dim3 cgrid((unsigned)(8 * std::min(per_xcd, 64)));
-            if (ksize == 1)
-                hipLaunchKernelGGL(corr_pool_kernel<1>, cgrid, dim3(256), CX_LDS, stream, fnA, fnB, nA, nB, C, P, (uint8_t *)nullptr,
-                                   2 * sWs, sWs, (size_t)0, gx, gy, (int)ntiles, per_xcd);
-            else if (ksize == 4)
-                hipLaunchKernelGGL(corr_pool_kernel<4>, cgrid, dim3(256), CX_LDS, stream, fnA, fnB, nA, nB, C, P, dout, 2 * sWs, sWs,
-                                   nel, gx, gy, (int)ntiles, per_xcd);
-            else
-                hipLaunchKernelGGL(corr_pool_kernel<2>, cgrid, dim3(256), CX_LDS, stream, fnA, fnB, nA, nB, C, P, dout, 2 * sWs, sWs,
-                                   nel, gx, gy, (int)ntiles, per_xcd);
-        }
-
-        const int col_groups = ceil_div(nBc, 256) * ceil_div(nAc, 64);
-        const dim3 mgrid(col_groups + ceil_div(nAc, 4), 1, nz);
-        hipLaunchKernelGGL(maxima_kernel, mgrid, dim3(256), 0, stream, P, nAc, nBc, rkey1, ckey1, sWs, sWs, (const float *)nullptr, col_groups);
-
-        // first mutual matching, in place on the pooled volume (+ max |X| for the consensus kernel's operand scale)
-        launch_mm_apply(P, nAc, nBc, rkey1, ckey1, P, sWs, sWs, sWs, xmax, nullptr, nz, stream);
-        if (ncn->gen) {   // a generic stack: layer by layer, the sum of its branches in Y
-            const int st = launch_nc_generic(*ncn->gen, P, sWs, Y, sWs, (float *)(base + ws.act), sWs, (int)nz, d0, d1, d2, d3, stream);
-            if (st != P2P_OK) return st;
-            Y2 = nullptr;
-        } else {   // both consensus layers, both branches: relu(.) of the direct branch into Y, of the transposed one into Y2
-            const int st = launch_nc_fused(P, Y, Y2, sWs, (int)nz, d0, d1, d2, d3, ncn->wfused, ncn->b2, xmax, sWs, ncn->tile, stream);
-            if (st != P2P_OK) return st;
-        }
-        hipLaunchKernelGGL(maxima_kernel, mgrid, dim3(256), 0, stream, Y, nAc, nBc, rkey2, ckey2, sWs, sWs, Y2, col_groups);
-        launch_mm_apply(Y, nAc, nBc, rkey2, ckey2, out, sWs, sWs, nel, nullptr, Y2, nz, stream);
-    }
-    return check_launch("coarse_forward kernels");
-}
-
-extern "C" int p2p_coarse_forward(const float *featA, const float *featB, int C, int hA, int wA, int hB, int wB,
-                                  int ksize, const p2p_ncn *ncn, float *corr4d_out, uint8_t *delta_out,
-                                  void *workspace, size_t workspace_bytes, p2p_stream_t stream) {
-    return p2p_coarse_forward_batch(featA, featB, 1, C, hA, wA, hB, wB, ksize, ncn, corr4d_out, delta_out, workspace,
-                                    workspace_bytes, stream);
-}
-
-extern "C" int p2p_neigh_consensus_batch(const float *x, int batch, int hA, int wA, int hB, int wB, const p2p_ncn *ncn, float *y_out,
-                                         void *workspace, size_t workspace_bytes, p2p_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    P2P_REQUIRE(x && ncn && y_out && workspace, P2P_EINVAL, "p2p_neigh_consensus: null argument");
-    P2P_REQUIRE(batch >= 1 && batch <= 65535 && hA > 0 && wA > 0 && hB > 0 && wB > 0, P2P_EINVAL, "p2p_neigh_consensus: bad sizes");
-    if (ncn->gen) {
-        const size_t cells = (size_t)hA * wA * hB * wB, per = nc_generic_ws_bytes(*ncn->gen, cells);
-        P2P_REQUIRE(workspace_bytes >= per, P2P_ENOMEM, "p2p_neigh_consensus: workspace %zu < %zu bytes (one volume)", workspace_bytes, per);
-        P2P_REQUIRE(((uintptr_t)workspace & 15) == 0, P2P_EINVAL, "p2p_neigh_consensus: the workspace of a generic handle must be 16-byte aligned");
-        const int per_launch = (int)std::min<size_t>(batch, workspace_bytes / per);      // volumes the workspace holds at once
-        for (int z0 = 0; z0 < batch; z0 += per_launch) {
-            const int st = launch_nc_generic(*ncn->gen, x + (size_t)z0 * cells, cells, y_out + (size_t)z0 * cells, cells, (float *)workspace,
-                                             per / sizeof(float), std::min(per_launch, batch - z0), hA, wA, hB, wB, stream);
-            if (st != P2P_OK) return st;
-        }
-        return P2P_OK;
-    }
-    P2P_REQUIRE(workspace_bytes >= (size_t)batch * sizeof(int), P2P_ENOMEM, "p2p_neigh_consensus: workspace of %zu bytes needed (4 per volume)",
-                (size_t)batch * sizeof(int));
-    const size_t nel = (size_t)hA * wA * hB * wB;
-    int *xmax = (int *)workspace;
-    P2P_HIP_CHECK(hipMemsetAsync(y_out, 0, (size_t)batch * nel * sizeof(float), stream));
-    P2P_HIP_CHECK(hipMemsetAsync(xmax, 0, (size_t)batch * sizeof(int), stream));
-    const int st = launch_absmax(x, nel, nel, batch, xmax, 1, stream);
-    if (st != P2P_OK) return st;
-    return launch_nc_fused(x, y_out, nullptr, nel, batch, hA, wA, hB, wB, ncn->wfused, ncn->b2, xmax, 1, ncn->tile, stream);
-}
-
-extern "C" int p2p_delta_unpack(const uint8_t *delta, size_t n, int ksize, int64_t *out, p2p_stream_t stream) {
-    P2P_REQUIRE(delta && out && ksize >= 1, P2P_EINVAL, "p2p_delta_unpack: bad argument");
-    if (n == 0) return P2P_OK;
-    hipLaunchKernelGGL(delta_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, delta, n,
-                       ksize, (long long *)out);
-    return check_launch("delta_unpack_kernel");
-}
-
-extern "C" int p2p_coarse_matches_batch(const float *corr4d, const uint8_t *delta, int batch, int hA, int wA, int hB, int wB,
-                                        int ksize, int upsample, int center, int64_t *matches_out, float *scores_out,
-                                        p2p_stream_t stream) {
-    P2P_REQUIRE(corr4d && matches_out && scores_out, P2P_EINVAL, "p2p_coarse_matches: null argument");
-    P2P_REQUIRE(batch >= 1 && batch <= 65535, P2P_EINVAL, "p2p_coarse_matches: batch %d out of range", batch);
-    P2P_REQUIRE(hA > 0 && wA > 0 && hB > 0 && wB > 0 && ksize >= 1, P2P_EINVAL, "p2p_coarse_matches: bad sizes");
-    P2P_REQUIRE(ksize == 1 || delta, P2P_EINVAL, "p2p_coarse_matches: delta required when ksize > 1");
-    const int nA = hA * wA, nB = hB * wB;
-    MatchArgs m{corr4d, delta, hA, wA, hB, wB, ksize, upsample, center, (long long *)matches_out, scores_out,
-                (size_t)nA * nB, (size_t)nA + nB};
-    hipLaunchKernelGGL(match_cols_kernel, dim3(ceil_div(nB, MC_COLS), 1, batch), dim3(256), 0, (hipStream_t)stream, m);
-    hipLaunchKernelGGL(match_rows_kernel, dim3(ceil_div(nA, 4), 1, batch), dim3(256), 0, (hipStream_t)stream, m);
-    return check_launch("match kernels");
-}
-
-extern "C" int p2p_coarse_matches_topk_batch(const float *corr4d, const uint8_t *delta, int batch, int hA, int wA, int hB, int wB,
-                                             int ksize, int upsample, int center, int topk, int do_softmax,
-                                             int64_t *matches_out, float *scores_out, p2p_stream_t stream) {
-    P2P_REQUIRE(corr4d && matches_out && scores_out, P2P_EINVAL, "p2p_coarse_matches_topk: null argument");
-    P2P_REQUIRE(batch >= 1 && batch <= 65535, P2P_EINVAL, "p2p_coarse_matches_topk: batch %d out of range", batch);
-    P2P_REQUIRE(hA > 0 && wA > 0 && hB > 0 && wB > 0 && ksize >= 1, P2P_EINVAL, "p2p_coarse_matches_topk: bad sizes");
-    P2P_REQUIRE(ksize == 1 || delta, P2P_EINVAL, "p2p_coarse_matches_topk: delta required when ksize > 1");
-    const int nA = hA * wA, nB = hB * wB;
-    P2P_REQUIRE(topk >= 1 && topk <= 8, P2P_EINVAL, "p2p_coarse_matches_topk: topk %d out of range (1 to 8)", topk);
-    P2P_REQUIRE(topk <= std::min(nA, nB), P2P_EINVAL, "p2p_coarse_matches_topk: topk %d exceeds the %d cells of an image", topk,
-                std::min(nA, nB));
-    MatchArgs m{corr4d, delta, hA, wA, hB, wB, ksize, upsample, center, (long long *)matches_out, scores_out,
-                (size_t)nA * nB, (size_t)topk * ((size_t)nA + nB)};
-    const int sm = do_softmax ? 1 : 0;
-    hipLaunchKernelGGL(match_cols_topk_kernel, dim3(ceil_div(nB, MC_COLS), 1, batch), dim3(256), 0, (hipStream_t)stream, m, topk, sm);
-    hipLaunchKernelGGL(match_rows_topk_kernel, dim3(ceil_div(nA, 4), 1, batch), dim3(256), 0, (hipStream_t)stream, m, topk, sm);
-    return check_launch("top-k match kernels");
-}
-
-extern "C" int p2p_coarse_matches(const float *corr4d, const uint8_t *delta, int hA, int wA, int hB, int wB, int ksize,
-                                  int upsample, int center, int64_t *matches_out, float *scores_out, p2p_stream_t stream) {
-    return p2p_coarse_matches_batch(corr4d, delta, 1, hA, wA, hB, wB, ksize, upsample, center, matches_out, scores_out, stream);
-}
+// sections 4 (its shape-generic part) and 5: no units of their own
+#include "consensus_generic.hip"
+#include "matches.hip"

@@ -29,7 +29,7 @@
 // (2^12 on X, per-channel on the layer-1 weights, one per branch on the hidden planes and the layer-2 weights) are undone
 // exactly.  The halo of the tile is recomputed ((TA+2)(TB+2)(TC+2)/(TA TB TC) of layer 1); HBM sees X once per tile
 // neighbourhood (L2 hits) and Y once.
-#include "p2p_common.h"
+#include "coarse_common.h"
 
 #include <algorithm>
 #include <cmath>

@@ -19,7 +19,7 @@
 // depends on the configuration alone -- not on the pair's position in the batch, the batch size or the workspace.
 // Device code is restricted to what the kernel emulator of the test-suite runs.  Compiled as part of coarse.hip.
 #pragma once
-#include "p2p_common.h"
+#include "coarse_common.h"
 
 #include <algorithm>
 #include <vector>

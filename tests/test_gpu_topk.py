@@ -34,6 +34,11 @@ def test_topk_against_restatement(case, lib, dev):
     tr.check_against_restatement(lib, case, dev)
 
 
+@pytest.mark.parametrize("case", list(tr.CASES))
+def test_one_candidate_against_restatement(case, lib, dev):
+    tr.check_one_candidate_against_restatement(lib, case, dev)
+
+
 @pytest.mark.parametrize("case", tr.GOLDEN_CASES)
 def test_topk_against_reference_golden(case, lib, dev):
     tr.check_against_golden(lib, case, dev)

@@ -1,6 +1,6 @@
-"""The top-k match extraction (match_cols_topk_kernel / match_rows_topk_kernel of csrc/coarse.hip behind
+"""The top-k match extraction (match_cols_topk_kernel / match_rows_topk_kernel of csrc/matches.hip behind
 p2p_coarse_matches_topk_batch) executed on the CPU by the test-suite's HIP stand-in (tests/hipemu): the torch restatement
-on every case of tests/topk_reference.py, the unmodified reference's outputs (tests/golden/topk_*.npz), the identity of
+on every case of tests/topk_reference.py (of the one-candidate entry as well), the unmodified reference's outputs (tests/golden/topk_*.npz), the identity of
 topk = 1 with the one-candidate kernels, and the argument checks."""
 import os
 import sys
@@ -22,6 +22,11 @@ def emu():
 @pytest.mark.parametrize("case", list(tr.CASES))
 def test_topk_against_restatement(case, emu):
     tr.check_against_restatement(emu, case)
+
+
+@pytest.mark.parametrize("case", list(tr.CASES))
+def test_one_candidate_against_restatement(case, emu):
+    tr.check_one_candidate_against_restatement(emu, case)
 
 
 @pytest.mark.parametrize("case", tr.GOLDEN_CASES)

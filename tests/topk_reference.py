@@ -22,6 +22,9 @@ CASES = {
     "K": dict(dims=(4, 4, 6, 6), batch=2, ksize=4, topks=(4,), upsample=4, center=False, seed=903),
     # planted ties (see inputs)
     "T": dict(dims=(5, 7, 6, 9), batch=1, ksize=2, topks=(3,), upsample=8, center=True, seed=904),
+    # nA 12 < the 16 row slices of the column kernels: four empty slices bring (-inf, 0x7fffffff) to the tree; nB 25 < one
+    # wave: 39 empty lanes in the row kernels, and a last block of 16 columns that holds 9
+    "N": dict(dims=(3, 4, 5, 5), batch=2, ksize=1, topks=(1, 3), upsample=16, center=True, seed=905),
 }
 GOLDEN_CASES = ("S", "W", "K")      # T has ties: torch.topk, which the reference calls, leaves their order open
 
@@ -144,29 +147,44 @@ def run_top1(lib, corr, delta, ksize, upsample, center):
     return m.cpu(), s.cpu()
 
 
-# ---- the three parity checks, shared by the emulated and the GPU test -------------------------------------------------------
+# ---- the parity checks, shared by the emulated and the GPU test -------------------------------------------------------
 def case_runs(case):
     c = CASES[case]
     return [(topk, sm) for topk in c["topks"] for sm in (True, False)]
 
 
-def check_against_restatement(lib, case, device="cpu"):
+def _assert_restated(what, m, s, rm, rs, sm):
     """Match rows exact (the tie rule of case T included), raw scores bit-equal, softmax scores within SCORE_TOL."""
+    assert m.shape == rm.shape and s.shape == rs.shape
+    bad = (m != rm).any(dim=-1)
+    assert not bad.any(), f"{what} softmax {sm}: {int(bad.sum())} rows differ, first {bad.nonzero()[0].tolist()}"
+    if sm:
+        err = (s - rs).abs().max().item()
+        print(f"{what}: softmax score error {err:.3g}")
+        assert err <= SCORE_TOL, err
+    else:
+        assert torch.equal(s.view(torch.int32), rs.view(torch.int32)), f"{what}: raw scores not bit-equal"
+
+
+def check_against_restatement(lib, case, device="cpu"):
     c = CASES[case]
     for topk, sm in case_runs(case):
         corr, delta = inputs(case, sm)
         rm, rs = restate(corr, delta, c["ksize"], c["upsample"], c["center"], topk, sm)
         m, s = run_topk(lib, corr.to(device), delta.to(device) if delta is not None else None, c["ksize"], c["upsample"],
                         c["center"], topk, sm)
-        assert m.shape == rm.shape and s.shape == rs.shape
-        bad = (m != rm).any(dim=-1)
-        assert not bad.any(), f"case {case} topk {topk} softmax {sm}: {int(bad.sum())} rows differ, first {bad.nonzero()[0].tolist()}"
-        if sm:
-            err = (s - rs).abs().max().item()
-            print(f"case {case} topk {topk}: softmax score error {err:.3g}")
-            assert err <= SCORE_TOL, err
-        else:
-            assert torch.equal(s.view(torch.int32), rs.view(torch.int32)), f"case {case} topk {topk}: raw scores not bit-equal"
+        _assert_restated(f"case {case} topk {topk}", m, s, rm, rs, sm)
+
+
+def check_one_candidate_against_restatement(lib, case, device="cpu"):
+    """p2p_coarse_matches_batch against the restatement with one candidate and softmax, at the bars of topk = 1 above: the
+    one-candidate kernels and the top-k kernels are one body, so their identity (check_top1_identity) compares that body
+    with itself."""
+    c = CASES[case]
+    corr, delta = inputs(case, True)
+    rm, rs = restate(corr, delta, c["ksize"], c["upsample"], c["center"], 1, True)
+    m, s = run_top1(lib, corr.to(device), delta.to(device) if delta is not None else None, c["ksize"], c["upsample"], c["center"])
+    _assert_restated(f"case {case} one candidate", m, s, rm, rs, True)
 
 
 def golden_name(case):
