@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from . import resnet
 from .utils import filter_coarse
-from .. import ops
+from .. import ops, staging
 
 
 class _Holder(nn.Module):
@@ -142,8 +142,7 @@ class Patch2Pix(nn.Module):
             self.regress_fine = self.regress_mid if self.shared else _Holder(_regressor_spec(self._layout))
         self.to(self.device)
         self._packed = None
-        self._pinned = {}        # up to 4 tickets in flight per shape
-        self._pin_turn = 0
+        self._ticket_ring = staging.PinnedRing(4)        # up to 4 tickets in flight
         self.init_weights_(weights_dict=config.weights_dict)
         self.eval()
 
@@ -305,37 +304,18 @@ class Patch2Pix(nn.Module):
         so that the host-side filter_coarse (reference networks/utils.py:38-72) never idles the GPU."""
         corr4d, delta4d = self.forward_coarse_match(feats1[-1], feats2[-1], ksize=ksize)
         matches_, score_ = self.cal_coarse_matches(corr4d, delta4d, ksize=ksize, upsample=self.upsample, center=True)
-        main = torch.cuda.current_stream(self.device)
-        # pinned staging buffers are recycled (allocating pinned memory synchronises with the device)
-        key = (tuple(matches_.shape), self._pin_turn)
-        self._pin_turn = (self._pin_turn + 1) % 4
-        if key not in self._pinned:
-            self._pinned[key] = [torch.empty(matches_.shape, dtype=matches_.dtype, pin_memory=True),
-                                 torch.empty(score_.shape, dtype=score_.dtype, pin_memory=True), None]
-        slot = self._pinned[key]
-        if slot[2] is not None and not slot[2].get("consumed", False):
-            # a fifth ticket of this shape while the first is still pending: its staging buffers are taken over, the
-            # old ticket falls back to its own device-to-host copy when (if) it is consumed
-            slot[2]["done"].synchronize()
-            slot[2]["stale"] = True
-        host_m, host_s = slot[0], slot[1]
         # The copies go to the stream that produced the arrays, in front of whatever the caller enqueues next: the
         # regress launch is one persistent work-group per compute unit, so a copy kernel on a side stream that becomes
         # ready when that launch has started would wait for its end (17 ms at 6400 proposals) -- and the host with it.
-        host_m.copy_(matches_, non_blocking=True)
-        host_s.copy_(score_, non_blocking=True)
-        done = torch.cuda.Event(blocking=True)
-        done.record(main)
-        ticket = dict(feats1=feats1, feats2=feats2, matches=matches_, scores=score_, host=(host_m, host_s), done=done)
-        slot[2] = ticket
-        return ticket
+        # A fifth ticket while the first is still pending takes over its staging slot: the old ticket then falls back
+        # to its own device-to-host copy when (if) it is consumed.
+        return dict(feats1=feats1, feats2=feats2, matches=matches_, scores=score_,
+                    staged=staging.readback([matches_, score_], self._ticket_ring))
 
     def fine_from_ticket(self, ticket, ncn_thres=0.0, mutual=True, return_all=False, ptmax=None):
-        ticket["done"].synchronize()
-        host_m, host_s = ticket["host"]
+        host = ticket["staged"].wait()          # None: the staging slot went to a later ticket
         coarse_matches, match_scores = filter_coarse(ticket["matches"], ticket["scores"], ncn_thres, mutual, ptmax=ptmax,
-                                                     host_copy=None if ticket.get("stale") else (host_m.numpy(), host_s.numpy()))
-        ticket["consumed"] = True          # its pinned staging slot may be reused
+                                                     host_copy=None if host is None else (host[0].numpy(), host[1].numpy()))
         coarse_matches = self.shift_to_anchors(coarse_matches)
         fine, fine_scores, mid, mid_scores = self._fine_chain(ticket["feats1"], ticket["feats2"], coarse_matches)
         if return_all:
@@ -382,13 +362,7 @@ class Patch2Pix(nn.Module):
         return self.fine_from_ticket(ticket, ncn_thres, mutual, return_all, ptmax)
 
     def _pyramids(self, im1, im2):
-        """The two pyramids; equally sized image batches go through the backbone as one batch (an image's pyramid does not
-        depend on its batch mates: tests/test_gpu_parity.py::test_backbone_batch_and_tile_independence)."""
-        if im1.shape == im2.shape and im1.is_cuda:
-            feats = self.extract.pyramid(torch.cat([im1, im2]))
-            n = im1.shape[0]
-            return [f[:n] for f in feats], [f[n:] for f in feats]
-        return self.extract.pyramid(im1), self.extract.pyramid(im2)
+        return resnet.pair_pyramids(self.extract, im1, im2)
 
     def predict_fine(self, im1, im2, ksize=2, ncn_thres=0.0, mutual=True, return_all=False):
         feats1, feats2 = self._pyramids(im1, im2)

@@ -161,3 +161,15 @@ class ResNet34(nn.Module):
 
     def forward(self, x, early_feat=True):
         return self.pyramid(x)[-1]
+
+
+def pair_pyramids(extract, im1, im2, both=None):
+    """The pyramids of two image batches; equally sized ones go through the backbone as one batch (an image's pyramid
+    does not depend on its batch mates: tests/test_gpu_parity.py::test_backbone_batch_and_tile_independence).  `both`:
+    the tensor `im1` and `im2` are the halves of, where the caller has it (saves the concatenation)."""
+    if both is None and im1.shape == im2.shape:
+        both = torch.cat([im1, im2])
+    if both is None:
+        return extract.pyramid(im1), extract.pyramid(im2)
+    feats, n = extract.pyramid(both), im1.shape[0]
+    return [f[:n] for f in feats], [f[n:] for f in feats]

@@ -13,6 +13,10 @@ row-wise unique runs on one packed 64-bit key per row (pixel coordinates are non
 import numpy as np
 import torch
 
+from .. import staging
+
+_ring = staging.PinnedRing(8)
+
 
 def _unique_rows(rows):
     """(first_index, counts) of the lexicographically sorted distinct rows of an int64 [n,4] array."""
@@ -59,39 +63,7 @@ def filter_coarse(coarse_matches, match_scores, ncn_thres=0.0, mutual=True, ptma
         out_scores.append(scores)
     # one upload for the whole batch, then per-item views
     counts = [r.shape[0] for r in out_rows]
-    rows_np, scores_np = np.concatenate(out_rows), np.concatenate(out_scores)
-    if device.type == "cuda":
-        # through recycled pinned buffers: a copy from pageable memory would block the host until the stream
-        # has drained, i.e. idle the GPU while the next launch is being prepared
-        pin_r, pin_s, done = _pinned(rows_np.shape[0], device)
-        pin_r[:rows_np.shape[0]].copy_(torch.from_numpy(rows_np))
-        pin_s[:rows_np.shape[0]].copy_(torch.from_numpy(scores_np))
-        all_rows = pin_r[:rows_np.shape[0]].to(device, non_blocking=True)
-        all_scores = pin_s[:rows_np.shape[0]].to(device, non_blocking=True)
-        done.record(torch.cuda.current_stream(device))      # the slot is reusable once this upload has run
-    else:
-        all_rows, all_scores = torch.from_numpy(rows_np), torch.from_numpy(scores_np)
+    # through the pinned staging ring: a copy from pageable memory would block the host until the stream has drained,
+    # i.e. idle the GPU while the next launch is being prepared
+    all_rows, all_scores = staging.upload([np.concatenate(out_rows), np.concatenate(out_scores)], device, _ring)
     return list(torch.split(all_rows, counts)), list(torch.split(all_scores, counts))
-
-
-_pin_rings = {}      # device index -> [ring of 8 slots, turn]
-
-
-def _pinned(n, device):
-    """(rows int64 [cap,4], scores f32 [cap], event) -- pinned staging buffers from a ring of 8 PER DEVICE (an event
-    belongs to the device of the stream it was recorded on; one process may drive several GPUs).  The event is recorded
-    by the caller after its asynchronous upload; a slot is handed out again only after that upload has completed, so a
-    host that runs more than 8 uploads ahead of the stream waits here instead of overwriting a buffer still being read."""
-    ring = _pin_rings.setdefault(device.index if device.index is not None else torch.cuda.current_device(), [[None] * 8, 0])
-    slot = ring[1] % 8
-    ring[1] += 1
-    buf = ring[0][slot]
-    if buf is not None:
-        buf[2].synchronize()
-    if buf is None or buf[0].shape[0] < n:
-        cap = max(1024, 1 << (max(n, 1) - 1).bit_length())
-        with torch.cuda.device(device):
-            buf = (torch.empty((cap, 4), dtype=torch.int64).pin_memory(), torch.empty((cap,), dtype=torch.float32).pin_memory(),
-                   torch.cuda.Event(blocking=True))
-        ring[0][slot] = buf
-    return buf

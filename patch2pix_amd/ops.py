@@ -6,7 +6,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, staging
 
 
 def _stream():
@@ -606,31 +606,14 @@ def filter_coarse_batch(matches, scores, ncn_thres=0.0, mutual=True):
     return out_m, out_s, counts
 
 
-_small_rings = {}      # device index -> [ring of 8 [pinned byte buffer, event], turn]
+_small_ring = staging.PinnedRing(8)
 
 
 def small_to_device(array, dtype, device):
-    """A small host array -> device tensor through a ring of pinned staging buffers (per device), asynchronously.  A copy
-    from pageable memory makes the host wait for everything queued on the stream before it; a caller that pipelines
-    batches must never do that."""
-    t = torch.as_tensor(array, dtype=dtype).contiguous()
-    device = torch.device(device)
-    nbytes = t.numel() * t.element_size()
-    ring = _small_rings.setdefault(device.index if device.index is not None else torch.cuda.current_device(), [[None] * 8, 0])
-    slot = ring[1] % 8
-    ring[1] += 1
-    buf = ring[0][slot]
-    if buf is not None:
-        buf[1].synchronize()               # the upload that last read this buffer has completed
-    if buf is None or buf[0].numel() < nbytes:
-        with torch.cuda.device(device):
-            buf = [torch.empty((max(4096, nbytes),), dtype=torch.uint8).pin_memory(), torch.cuda.Event(blocking=True)]
-        ring[0][slot] = buf
-    host = buf[0][:nbytes].view(dtype).view(t.shape)
-    host.copy_(t)
-    out = host.to(device, non_blocking=True)
-    buf[1].record(torch.cuda.current_stream(device))
-    return out
+    """A small host array -> device tensor through the pinned staging ring (staging.py), asynchronously.  A copy from
+    pageable memory makes the host wait for everything queued on the stream before it; a caller that pipelines batches
+    must never do that."""
+    return staging.upload([torch.as_tensor(array, dtype=dtype)], device, _small_ring)[0]
 
 
 def match_tail_batch(fine, scores, coarse, counts, scale, io_thres):

@@ -9,6 +9,8 @@ import numpy as np
 import torch
 from PIL import Image
 
+from ... import staging
+
 _MEAN = np.array([0.485, 0.456, 0.406], dtype=np.float32).reshape(3, 1, 1)
 _STD = np.array([0.229, 0.224, 0.225], dtype=np.float32).reshape(3, 1, 1)
 
@@ -203,36 +205,13 @@ def resize_pixels_device(pixels, out_hw, normalise=False, out=None):
     return out
 
 
-_decode_pool = {}       # device -> ring of [pinned byte buffer, event-or-None] for the decoded (original size) pixels
+_decode_ring = staging.PinnedRing(4)
 
 
 def upload_pixels(arrays, device):
     """uint8 [H,W,3] numpy arrays of any sizes -> device tensors, through ONE recycled pinned buffer and one
-    asynchronous copy (a copy from pageable memory would make the host wait for the stream)."""
-    device = torch.device(device)
-    sizes = [(a.size + 255) & ~255 for a in arrays]
-    total = sum(sizes)
-    ring = _decode_pool.setdefault(str(device), {"slots": [], "turn": 0})
-    if len(ring["slots"]) < 4:
-        ring["slots"].append([None, None])
-    slot = ring["slots"][ring["turn"] % len(ring["slots"])]
-    ring["turn"] += 1
-    if slot[1] is not None:
-        slot[1].synchronize()              # the copy that last read this buffer has finished
-    if slot[0] is None or slot[0].numel() < total:
-        slot[0] = torch.empty((total + total // 2,), dtype=torch.uint8).pin_memory()
-    host, at = slot[0].numpy(), 0
-    for a, n in zip(arrays, sizes):
-        np.copyto(host[at:at + a.size], a.reshape(-1))
-        at += n
-    dev = slot[0][:total].to(device, non_blocking=True)
-    slot[1] = torch.cuda.Event(blocking=True)
-    slot[1].record(torch.cuda.current_stream(device))
-    out, at = [], 0
-    for a, n in zip(arrays, sizes):
-        out.append(dev[at:at + a.size].view(a.shape))
-        at += n
-    return out
+    asynchronous copy (staging.py; a copy from pageable memory would make the host wait for the stream)."""
+    return staging.upload(arrays, device, _decode_ring)
 
 
 def decode_pixels(im_path, k_size=2, upsample=16, imsize=None):

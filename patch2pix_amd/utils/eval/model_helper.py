@@ -12,6 +12,7 @@ Return contract of `estimate_matches` (reference :64-109):
     coarse_matches  float64 [M,4]  the coarse match each row was refined from (same as matches for eval_type='coarse')
 """
 from argparse import Namespace
+from concurrent.futures import ThreadPoolExecutor
 from functools import partial
 
 import numpy as np
@@ -88,22 +89,22 @@ def _call_coarse(net, args, imq, imr):
 
 
 # ------------------------------------------------------------------------------------------ matching
-_decoders = None        # two threads: the second image of a pair is decoded while the first one is (PIL releases the GIL)
+# the second image of a pair is decoded while the first one is (PIL releases the GIL); the threads start with the first job
+_decoders = ThreadPoolExecutor(max_workers=2, thread_name_prefix="p2p-decode")
+
+
+def _decode_pair(decode, net, im1, im2, ksize, imsize):
+    """`decode(im, ksize, upsample, imsize=)` of both images, the second one on the helper thread."""
+    second = _decoders.submit(decode, im2, ksize, net.upsample, imsize=imsize)
+    return decode(im1, ksize, net.upsample, imsize=imsize), second.result()
 
 
 def _load_pair(net, im1, im2, ksize, imsize):
     """Both images as [1,3,H,W] tensors on the device + the (1,4) factors back to original pixels."""
-    global _decoders
-    if _decoders is None:
-        from concurrent.futures import ThreadPoolExecutor
-        _decoders = ThreadPoolExecutor(max_workers=2, thread_name_prefix="p2p-decode")
     # PIL decode + bicubic resize on the host like the reference (load_im_flexible); the uint8 pixels go to the device and
     # are normalised there (bit-identical, a quarter of the upload)
-    second = _decoders.submit(load_im_pixels, im2, ksize, net.upsample, imsize=imsize)
-    loaded = [load_im_pixels(im1, ksize, net.upsample, imsize=imsize), None]
-    loaded[1] = second.result()
     tensors, factors = [], ()
-    for pixels, scale_wh in loaded:
+    for pixels, scale_wh in _decode_pair(load_im_pixels, net, im1, im2, ksize, imsize):
         tensors.append(normalise_pixels(pixels.unsqueeze(0).to(net.device)))
         factors += tuple(scale_wh)
     return tensors[0], tensors[1], np.array([factors])
@@ -112,13 +113,7 @@ def _load_pair(net, im1, im2, ksize, imsize):
 def _load_pair_device(net, im1, im2, ksize, imsize):
     """`_load_pair` with only the decoding on the host: the original pixels of both images go up in one copy and are
     resized (Pillow's bicubic, bit for bit) and normalised on the device."""
-    global _decoders
-    if _decoders is None:
-        from concurrent.futures import ThreadPoolExecutor
-        _decoders = ThreadPoolExecutor(max_workers=2, thread_name_prefix="p2p-decode")
-    second = _decoders.submit(decode_pixels, im2, ksize, net.upsample, imsize=imsize)
-    decoded = [decode_pixels(im1, ksize, net.upsample, imsize=imsize), None]
-    decoded[1] = second.result()
+    decoded = _decode_pair(decode_pixels, net, im1, im2, ksize, imsize)
     pixels = upload_pixels([d[0] for d in decoded], net.device)
     tensors = [resize_pixels_device(p, d[1], normalise=True) for p, d in zip(pixels, decoded)]
     return tensors[0], tensors[1], np.array([tuple(decoded[0][2]) + tuple(decoded[1][2])])

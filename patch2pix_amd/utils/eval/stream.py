@@ -19,6 +19,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
+from ...networks.resnet import pair_pyramids
+from ... import staging
 from ..datasets.preprocess import decode_pixels, load_im_pixels, normalise_pixels, resize_pixels_device, upload_pixels
 
 
@@ -42,32 +44,14 @@ def _load(job):
     return idx, t1, t2, np.array([tuple(s1) + tuple(s2)]), job
 
 
-_pin_pool = {}      # (device, shape) -> ring of [pinned tensor, event-or-None] staging buffers for the image batches
+_image_ring, _out_ring, _dev_ring = staging.PinnedRing(4), staging.PinnedRing(4), staging.PinnedRing(4)
 
 
 def _upload(tensors, device):
     """Stack a list of equally shaped uint8 [H,W,3] images into a recycled PINNED batch buffer, start one asynchronous
     copy to the device and normalise there -> float32 [B,3,H,W].  (Stacking into pageable memory and copying from there cost 100-190 ms per batch of 8 pairs --
     more than the whole GPU work of the batch.)"""
-    if torch.device(device).type != "cuda":            # host-logic tests drive the generator with a CPU stand-in of the net
-        return normalise_pixels(torch.stack(tensors).to(device))
-    shape = (len(tensors),) + tuple(tensors[0].shape)
-    ring = _pin_pool.setdefault((str(torch.device(device)), shape), {"slots": [], "turn": 0})     # an event belongs to its device
-    if len(ring["slots"]) < 4:
-        ring["slots"].append([torch.empty(shape, dtype=tensors[0].dtype).pin_memory(), None])
-    slot = ring["slots"][ring["turn"] % len(ring["slots"])]
-    ring["turn"] += 1
-    if slot[1] is not None:
-        slot[1].synchronize()              # the copy that last read this buffer has finished
-    # plain memcpys: torch.stack would fan this copy out over an OpenMP team as wide as the machine, whose spin-waiting
-    # threads burn a container's CPU quota within milliseconds (measured: 80 ms stalls of every thread of the process)
-    dst = slot[0].numpy()
-    for i, t in enumerate(tensors):
-        np.copyto(dst[i], t.numpy())
-    dev = slot[0].to(device, non_blocking=True)
-    slot[1] = torch.cuda.Event(blocking=True)
-    slot[1].record(torch.cuda.current_stream(device))
-    return normalise_pixels(dev)
+    return normalise_pixels(staging.upload(tensors, device, _image_ring, stack=True))
 
 
 def _upload_resize(first, second, device):
@@ -83,7 +67,12 @@ def _upload_resize(first, second, device):
             resize_pixels_device(pixels[n:], second[0].shape[:2], normalise=True), None)
 
 
-_out_pool = {}      # device -> {"slots": [[pinned [cap, 9] tensor, event-or-None], ...], "turn": int}: staging of the match arrays
+def _staged(rec):
+    """The host arrays of an issued batch, once its copy has run."""
+    views = rec["staged"].wait()
+    if views is None:
+        raise RuntimeError("estimate_matches_stream: more batches in flight than staging slots")
+    return [v.numpy() for v in views]
 
 
 def _issue_fine(net, ticket, metas, ncn_thres, mutual):
@@ -93,28 +82,11 @@ def _issue_fine(net, ticket, metas, ncn_thres, mutual):
     counts = [f.shape[0] for f in fine]
     # one device-to-host copy for the whole batch: [fine x1,y1,x2,y2 | confidence | coarse x1,y1,x2,y2]
     packed = torch.cat([torch.cat(fine), torch.cat(conf)[:, None], torch.cat(coarse).float()], dim=1)
-    if packed.device.type != "cuda":
-        return dict(host=packed, n=packed.shape[0], counts=counts, metas=metas, event=None)
-    n = packed.shape[0]
-    ring = _out_pool.setdefault(str(packed.device), {"slots": [], "turn": 0})
-    if len(ring["slots"]) < 4:
-        ring["slots"].append([None, None])
-    slot = ring["slots"][ring["turn"] % len(ring["slots"])]
-    ring["turn"] += 1
-    if slot[1] is not None:
-        slot[1].synchronize()              # the copy that last wrote this buffer has finished (and was collected: FIFO)
-    if slot[0] is None or slot[0].shape[0] < n:
-        slot[0] = torch.empty((max(n + n // 2, 4096), 9), dtype=torch.float32).pin_memory()
-    slot[0][:n].copy_(packed, non_blocking=True)
-    slot[1] = torch.cuda.Event(blocking=True)
-    slot[1].record(torch.cuda.current_stream(packed.device))
-    return dict(host=slot[0], n=n, counts=counts, metas=metas, event=slot[1], keep=packed)
+    return dict(staged=staging.readback([packed], _out_ring), counts=counts, metas=metas)
 
 
 def _collect(rec, io_thres):
-    if rec["event"] is not None:
-        rec["event"].synchronize()
-    packed = rec["host"][:rec["n"]].numpy()
+    packed, = _staged(rec)
     out, start = [], 0
     for n, to_original in zip(rec["counts"], rec["metas"]):
         rows = packed[start:start + n]
@@ -127,9 +99,6 @@ def _collect(rec, io_thres):
     return out
 
 
-_dev_pool = {}      # (device, shapes) -> ring of pinned staging buffers for the padded outputs of the device path
-
-
 def _issue_device(net, f1, f2, group, ksize, ncn_thres, mutual, io_thres):
     """Coarse stage, device-side filter_coarse, both regressors and the io_thres / scaling tail of the batch enqueued,
     the padded results on their way to pinned memory.  Nothing here waits for the GPU."""
@@ -137,24 +106,11 @@ def _issue_device(net, f1, f2, group, ksize, ncn_thres, mutual, io_thres):
     fine, scores, coarse, counts = net.predict_fine_device(f1, f2, ksize=ksize, ncn_thres=ncn_thres, mutual=mutual)
     scale = np.concatenate([g[3] for g in group]).astype(np.float64)
     outs = ops.match_tail_batch(fine, scores, coarse, counts, scale, io_thres)
-    key = (str(fine.device),) + tuple(tuple(o.shape) for o in outs)
-    ring = _dev_pool.setdefault(key, {"slots": [], "turn": 0})
-    if len(ring["slots"]) < 4:
-        ring["slots"].append([[torch.empty(o.shape, dtype=o.dtype).pin_memory() for o in outs], None])
-    slot = ring["slots"][ring["turn"] % len(ring["slots"])]
-    ring["turn"] += 1
-    if slot[1] is not None:
-        slot[1].synchronize()
-    for h, o in zip(slot[0], outs):
-        h.copy_(o, non_blocking=True)
-    slot[1] = torch.cuda.Event(blocking=True)
-    slot[1].record(torch.cuda.current_stream(fine.device))
-    return dict(host=slot[0], event=slot[1], keep=outs, jobs=[g[4] for g in group])
+    return dict(staged=staging.readback(outs, _dev_ring), jobs=[g[4] for g in group])
 
 
 def _collect_device(net, rec, ncn_thres, mutual, io_thres):
-    rec["event"].synchronize()
-    m, s, c, n = [h.numpy() for h in rec["host"]]
+    m, s, c, n = _staged(rec)
     out = []
     for b, job in enumerate(rec["jobs"]):
         k = int(n[b])
@@ -228,12 +184,7 @@ def estimate_matches_stream(net, pairs, ksize=2, ncn_thres=0.0, mutual=True, io_
             else:
                 im1 = _upload([g[1] for g in group], net.device)
                 im2 = _upload([g[2] for g in group], net.device)
-            if im1.shape == im2.shape:
-                feats = net.extract.pyramid(both if both is not None else torch.cat([im1, im2]))
-                n = im1.shape[0]
-                f1, f2 = [f[:n] for f in feats], [f[n:] for f in feats]
-            else:
-                f1, f2 = net.extract.pyramid(im1), net.extract.pyramid(im2)
+            f1, f2 = pair_pyramids(net.extract, im1, im2, both)
             if on_device:
                 issued.append(_issue_device(net, f1, f2, group, ksize, ncn_thres, mutual, io_thres))
             else:
