@@ -69,7 +69,9 @@ int p2p_ncn_set_tile(p2p_ncn *ncn, int ta, int tb, int tc);
  * P2P_EINVAL; both before the device is touched.  The released shape is accepted too (that is how the generic path is compared
  * with the tuned one); p2p_ncn_create keeps producing tuned handles.  Every coarse entry point takes either kind;
  * p2p_ncn_set_tile refuses a generic handle (P2P_EUNSUPPORTED).  A generic handle's results do not depend on the batch, the
- * pair's position in it or the workspace size: every output cell sums its terms in an order the configuration alone fixes. */
+ * pair's position in it or the workspace size: every output cell sums its terms in an order the configuration alone fixes.
+ * Like every constructor of this library it packs on the host and uploads once: a device allocation that fails -> P2P_ENOMEM,
+ * a copy that fails -> P2P_EHIP (nothing stays allocated). */
 typedef struct p2p_ncn_config { int n_layers, kernel_size[4], channels[4], symmetric; } p2p_ncn_config;
 typedef struct p2p_ncn_tensors { const float *w[4], *b[4]; } p2p_ncn_tensors;
 int p2p_ncn_create_config(const p2p_ncn_config *config, const p2p_ncn_tensors *tensors, p2p_ncn **out);
@@ -141,7 +143,8 @@ int p2p_regressor_get_mode(const p2p_regressor *reg);
  * generic path is compared with the tuned one); p2p_regressor_create keeps producing tuned handles.
  * Tensors: HOST pointers to the state_dict tensors, conv_w[i] = conv.{2i}.weight [conv_dim[i], c_in, k, k] (c_in of layer 0:
  * the selected channels, twice for 'pre'), conv_bn[i] = conv.{2i+1}.*, fc_w/fc_b[i] = fc.{3i}.*, fc_bn[i] = fc.{3i+1}.*,
- * out_w/out_b = fc.{3 n_fc}.* [5, k], [5].                                                                          */
+ * out_w/out_b = fc.{3 n_fc}.* [5, k], [5].  A device allocation that fails -> P2P_ENOMEM, a copy that fails -> P2P_EHIP
+ * (every constructor of the library; p2p_regressor_set_mode, which uploads a mode's weight stream on its first selection, too). */
 #define P2P_FEAT_COMB_PRE  0
 #define P2P_FEAT_COMB_POST 1
 typedef struct p2p_regressor_config {

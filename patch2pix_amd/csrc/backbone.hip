@@ -14,7 +14,7 @@
 // v_mfma_f32_32x32x16_f16 (a0 b0 + a0 b1 + a1 b0).  Chunks are double buffered: the global loads of chunk c + 1 are in
 // flight during the MFMAs of chunk c, one barrier per chunk.  Epilogue: acc x (BN scale / weight scale / activation
 // scale) + BN shift [+ skip] [ReLU] -> fp32 NHWC (32 consecutive channels of a pixel per half wave), running max.
-#include "p2p_common.h"
+#include "host_pack.h"
 
 #include <algorithm>
 #include <cmath>
@@ -467,8 +467,9 @@ static ConvCfg conv_cfg(int co, int ks, int stride, long tiles128, const int *fo
 }  // namespace p2p
 
 struct p2p_conv {
-    unsigned char *wq;
-    float *sc, *sh;          // one allocation behind wq
+    p2p::DeviceBlob blob;    // the one allocation behind the three pointers
+    const unsigned char *wq;
+    const float *sc, *sh;
     int ci, co, ks, stride;
     int tile[3];             // forced (mt, nt, wn); 0 = by the launch size
 };
@@ -488,71 +489,51 @@ extern "C" int p2p_conv_create(const float *weight, const p2p_bn_params *bn, int
     P2P_REQUIRE(stride == 1 || co % 128 == 0, P2P_EUNSUPPORTED, "p2p_conv_create: stride 2 with %d output channels", co);
     const int ck = conv_ck(stride), nchunks = ci / ck, spc = ck / 16, nsl = ks * ks * spc, ntiles = co / 32;
     const size_t wbytes = ((size_t)nchunks * nsl + 3) * ntiles * 2048;      // + the slabs of zeros the prefetch runs into
-    std::vector<unsigned char> h(wbytes + 2 * (size_t)co * 4, 0);
-    float *sc = (float *)(h.data() + wbytes), *sh = sc + co;
+    p2p_conv *cv = new p2p_conv{};
+    DeviceBlob &b = cv->blob;
+    const size_t o_w = b.take<unsigned char>(wbytes), o_sc = b.take<float>(co), o_sh = b.take<float>(co);
+    unsigned char *h = b.at<unsigned char>(o_w);
+    float *sc = b.at<float>(o_sc);
+    fold_bn(*bn, co, sc, b.at<float>(o_sh));
     std::vector<int> sw(co);
     for (int o = 0; o < co; ++o) {
         float mx = 0.f;
         for (int i = 0; i < ci * ks * ks; ++i) mx = std::max(mx, std::fabs(weight[(size_t)o * ci * ks * ks + i]));
-        int e = 0;
-        if (mx > 0.f && std::isfinite(mx)) { std::frexp(mx, &e); e = 12 - e; }
-        sw[o] = e;
-        const float inv = 1.0f / std::sqrt(bn->running_var[o] + 1e-5f);
-        const float s = bn->weight[o] * inv;
-        sc[o] = std::ldexp(s, -e);
-        sh[o] = bn->bias[o] - bn->running_mean[o] * s;
+        sw[o] = pow2_exponent_to(mx, 12);
+        sc[o] = std::ldexp(sc[o], -sw[o]);
     }
     {
         for (int c = 0; c < nchunks; ++c)
             for (int tap = 0; tap < ks * ks; ++tap)
                 for (int sl = 0; sl < spc; ++sl)
                     for (int j = 0; j < ntiles; ++j) {
-                        uint16_t *frag = (uint16_t *)(h.data() + ((((size_t)c * ks * ks + tap) * spc + sl) * ntiles + j) * 2048);
+                        uint16_t *frag = (uint16_t *)(h + ((((size_t)c * ks * ks + tap) * spc + sl) * ntiles + j) * 2048);
                         for (int lane = 0; lane < 64; ++lane)
                             for (int e8 = 0; e8 < 8; ++e8) {
                                 const int o = j * 32 + (lane & 31), i = c * ck + sl * 16 + (lane >> 5) * 8 + e8;
                                 const float v = std::ldexp(weight[(((size_t)o * ci + i) * ks + tap / ks) * ks + tap % ks], sw[o]);
-                                const _Float16 h0 = (_Float16)v;
-                                const _Float16 h1 = (_Float16)(v - (float)h0);
-                                frag[lane * 8 + e8] = __builtin_bit_cast(uint16_t, h0);
-                                frag[512 + lane * 8 + e8] = __builtin_bit_cast(uint16_t, h1);
+                                split_fp16_planes(v, &frag[lane * 8 + e8], &frag[512 + lane * 8 + e8]);
                             }
                     }
     }
-    p2p_conv *cv = new p2p_conv{};
     cv->ci = ci; cv->co = co; cv->ks = ks; cv->stride = stride;
-    if (hipMalloc((void **)&cv->wq, h.size()) != hipSuccess) {
+    const int st = b.upload("p2p_conv_create: the packed weights");
+    if (st != P2P_OK) {
         delete cv;
-        set_error("p2p_conv_create: hipMalloc of %zu bytes failed", h.size());
-        return P2P_ENOMEM;
+        return st;
     }
-    if (hipMemcpy(cv->wq, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(cv->wq);
-        delete cv;
-        set_error("p2p_conv_create: upload failed");
-        return P2P_EHIP;
-    }
-    cv->sc = (float *)(cv->wq + wbytes);
-    cv->sh = cv->sc + co;
+    cv->wq = b.dev<unsigned char>(o_w); cv->sc = b.dev<float>(o_sc); cv->sh = b.dev<float>(o_sh);
     *out = cv;
     return P2P_OK;
 }
 
-extern "C" void p2p_conv_destroy(p2p_conv *cv) {
-    if (!cv) return;
-    (void)hipFree(cv->wq);
-    delete cv;
-}
+extern "C" void p2p_conv_destroy(p2p_conv *cv) { delete cv; }
 
 template <int MT, int NT, int WN, int NIT, int DB>
 static int launch_conv(const ConvArgs &a, dim3 grid, size_t lds, hipStream_t stream) {
     static DeviceOnce attr_set;
-    int dev = 0;
-    P2P_HIP_CHECK(hipGetDevice(&dev));
-    if (!attr_set.done(dev)) {
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)conv_kernel<MT, NT, WN, NIT, DB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set.set(dev);
-    }
+    const int dev = raise_lds_limit(attr_set, {{(const void *)conv_kernel<MT, NT, WN, NIT, DB>, 160 * 1024}});
+    if (dev < 0) return dev;
     hipLaunchKernelGGL((conv_kernel<MT, NT, WN, NIT, DB>), grid, dim3(256), lds, stream, a);
     return check_launch("conv_kernel");
 }
@@ -600,24 +581,24 @@ extern "C" int p2p_absmax_batch(const float *x, size_t count, int items, int *ou
 }
 
 struct p2p_stem {
-    unsigned char *wq;
-    float *sc, *sh;
+    p2p::DeviceBlob blob;    // the one allocation behind the three pointers
+    const unsigned char *wq;
+    const float *sc, *sh;
 };
 
 extern "C" int p2p_stem_create(const float *weight, const p2p_bn_params *bn, p2p_stem **out) {
     P2P_REQUIRE(weight && bn && out, P2P_EINVAL, "p2p_stem_create: null argument");
-    const size_t wbytes = 2 * 14 * 2 * 1024;
-    std::vector<unsigned char> h(wbytes + 2 * 64 * 4, 0);
-    float *sc = (float *)(h.data() + wbytes), *sh = sc + 64;
+    p2p_stem *st = new p2p_stem{};
+    DeviceBlob &b = st->blob;
+    const size_t o_w = b.take<unsigned char>(2 * 14 * 2 * 1024), o_sc = b.take<float>(64), o_sh = b.take<float>(64);
+    unsigned char *h = b.at<unsigned char>(o_w);
+    float *sc = b.at<float>(o_sc);
+    fold_bn(*bn, 64, sc, b.at<float>(o_sh));
     for (int o = 0; o < 64; ++o) {
         float mx = 0.f;
         for (int i = 0; i < 147; ++i) mx = std::max(mx, std::fabs(weight[o * 147 + i]));
-        int e = 0;
-        if (mx > 0.f && std::isfinite(mx)) { std::frexp(mx, &e); e = 12 - e; }
-        const float inv = 1.0f / std::sqrt(bn->running_var[o] + 1e-5f);
-        const float s = bn->weight[o] * inv;
-        sc[o] = std::ldexp(s, -e);
-        sh[o] = bn->bias[o] - bn->running_mean[o] * s;
+        const int e = pow2_exponent_to(mx, 12);
+        sc[o] = std::ldexp(sc[o], -e);
         // A fragment: lane (row = channel o & 31, K block lane >> 5), k = slab * 16 + 8 (lane >> 5) + j = (ky, half, kx pair, c)
         for (int sl = 0; sl < 14; ++sl)
             for (int kb = 0; kb < 2; ++kb)
@@ -625,37 +606,22 @@ extern "C" int p2p_stem_create(const float *weight, const p2p_bn_params *bn, p2p
                     const int ky = sl >> 1, kx = 4 * (sl & 1) + 2 * kb + (j >> 2), c = j & 3;
                     float v = 0.f;
                     if (kx < 7 && c < 3) v = std::ldexp(weight[((o * 3 + c) * 7 + ky) * 7 + kx], e);
-                    const _Float16 h0 = (_Float16)v;
-                    const _Float16 h1 = (_Float16)(v - (float)h0);
-                    uint16_t *frag = (uint16_t *)(h.data() + (((size_t)(o >> 5) * 14 + sl) * 2) * 1024);
+                    uint16_t *frag = (uint16_t *)(h + (((size_t)(o >> 5) * 14 + sl) * 2) * 1024);
                     const int lane = kb * 32 + (o & 31);
-                    frag[lane * 8 + j] = __builtin_bit_cast(uint16_t, h0);
-                    frag[512 + lane * 8 + j] = __builtin_bit_cast(uint16_t, h1);
+                    split_fp16_planes(v, &frag[lane * 8 + j], &frag[512 + lane * 8 + j]);
                 }
     }
-    p2p_stem *st = new p2p_stem{};
-    if (hipMalloc((void **)&st->wq, h.size()) != hipSuccess) {
+    const int rc = b.upload("p2p_stem_create: the packed weights");
+    if (rc != P2P_OK) {
         delete st;
-        set_error("p2p_stem_create: hipMalloc failed");
-        return P2P_ENOMEM;
+        return rc;
     }
-    if (hipMemcpy(st->wq, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(st->wq);
-        delete st;
-        set_error("p2p_stem_create: upload failed");
-        return P2P_EHIP;
-    }
-    st->sc = (float *)(st->wq + wbytes);
-    st->sh = st->sc + 64;
+    st->wq = b.dev<unsigned char>(o_w); st->sc = b.dev<float>(o_sc); st->sh = b.dev<float>(o_sh);
     *out = st;
     return P2P_OK;
 }
 
-extern "C" void p2p_stem_destroy(p2p_stem *st) {
-    if (!st) return;
-    (void)hipFree(st->wq);
-    delete st;
-}
+extern "C" void p2p_stem_destroy(p2p_stem *st) { delete st; }
 
 extern "C" int p2p_stem_forward(const p2p_stem *st, const float *image, const int *imax, int n, int h, int w, float *y, p2p_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;

@@ -416,14 +416,10 @@ __global__ __launch_bounds__(256, 2) void corr_pool_kernel(const unsigned short 
 
 int launch_corr_pool(const unsigned short *fnA, const unsigned short *fnB, int nA, int nB, int C, int ksize, float *P, uint8_t *delta,
                      size_t sAB, size_t sP, size_t sDelta, unsigned nz, hipStream_t stream) {
-    int dev = 0;
-    P2P_HIP_CHECK(hipGetDevice(&dev));
     static DeviceOnce attr_set_dev;      // per device: a process may drive several GPUs
-    if (!attr_set_dev.done(dev)) {
-        for (const void *kernel : {(const void *)corr_pool_kernel<1>, (const void *)corr_pool_kernel<2>, (const void *)corr_pool_kernel<4>})
-            P2P_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CX_LDS));
-        attr_set_dev.set(dev);
-    }
+    const int dev = raise_lds_limit(attr_set_dev, {{(const void *)corr_pool_kernel<1>, CX_LDS}, {(const void *)corr_pool_kernel<2>, CX_LDS},
+                                                   {(const void *)corr_pool_kernel<4>, CX_LDS}});
+    if (dev < 0) return dev;
     const int gx = ceil_div(nB, CT), gy = ceil_div(nA, CT);
     const long long ntiles = (long long)gx * gy * nz;
     P2P_REQUIRE(ntiles < (1ll << 30), P2P_EUNSUPPORTED, "p2p_coarse_forward: %lld correlation tiles in one launch", ntiles);

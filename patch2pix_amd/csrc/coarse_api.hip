@@ -1,4 +1,4 @@
-// Coarse stage, host side: the p2p_ncn handle (the fused kernel's packed weights or a generic stack), the carve-up of the caller's
+// Coarse stage, host side: the p2p_ncn handle (the fused kernel's packed weights in a DeviceBlob, host_pack.h, or a generic stack), the carve-up of the caller's
 // workspace, and the p2p_coarse_* / p2p_neigh_consensus_* / p2p_delta_unpack entry points of include/p2p_hip.h.  No kernel lives
 // here and none is launched from here: every kernel sits next to its launcher (coarse.hip, matches.hip, consensus.hip,
 // consensus_generic.hip; declared in coarse_common.h).  Compiled as part of api.hip, not as a unit of its own.
@@ -33,17 +33,11 @@ extern "C" int p2p_ncn_create(const float *w1, const float *b1, const float *w2,
     P2P_REQUIRE(w1 && b1 && w2 && b2 && out, P2P_EINVAL, "p2p_ncn_create: null argument");
     // stored layout (conv4d.py:119-120): w1s[da][o][ci=0][db][dc][dd], w2s[da][o=0][ci][db][dc][dd] -> MFMA fragments of
     // both branches (consensus.hip)
-    std::vector<unsigned char> wf;
+    DeviceBlob wf;
     pack_nc_fused(w1, b1, w2, wf);
-    unsigned char *wfd = nullptr;
-    hipError_t e = hipMalloc(&wfd, wf.size());
-    if (e == hipSuccess) e = hipMemcpy(wfd, wf.data(), wf.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (wfd) (void)hipFree(wfd);
-        set_error("upload of the consensus weights failed: %s", hipGetErrorString(e));
-        return P2P_EHIP;
-    }
-    *out = new p2p_ncn{b2[0], wfd, {0, 0, 0}, nullptr};
+    const int st = wf.upload("p2p_ncn_create: the consensus weights");
+    if (st != P2P_OK) return st;
+    *out = new p2p_ncn{b2[0], std::move(wf), {0, 0, 0}, nullptr};
     return P2P_OK;
 }
 
@@ -52,7 +46,7 @@ extern "C" int p2p_ncn_create_config(const p2p_ncn_config *config, const p2p_ncn
     NcGen *g = nullptr;
     const int st = nc_generic_create(config, tensors, &g);      // validates before it touches the device
     if (st != P2P_OK) return st;
-    *out = new p2p_ncn{0.f, nullptr, {0, 0, 0}, g};
+    *out = new p2p_ncn{0.f, DeviceBlob(), {0, 0, 0}, g};
     return P2P_OK;
 }
 
@@ -69,12 +63,7 @@ extern "C" int p2p_ncn_set_tile(p2p_ncn *ncn, int ta, int tb, int tc) {
     return P2P_OK;
 }
 
-extern "C" void p2p_ncn_destroy(p2p_ncn *ncn) {
-    if (!ncn) return;
-    if (ncn->wfused) (void)hipFree(ncn->wfused);
-    nc_generic_destroy(ncn->gen);
-    delete ncn;
-}
+extern "C" void p2p_ncn_destroy(p2p_ncn *ncn) { delete ncn; }
 
 extern "C" size_t p2p_coarse_workspace_bytes(int channels, int hA, int wA, int hB, int wB, int ksize) {
     if (channels <= 0 || hA <= 0 || wA <= 0 || hB <= 0 || wB <= 0 || ksize < 1) return 0;
@@ -139,7 +128,7 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
             st = launch_nc_generic(*ncn->gen, P, sWs, Y, sWs, (float *)(base + ws.act), sWs, (int)nz, d0, d1, d2, d3, stream);
             Y2 = nullptr;
         } else {   // both consensus layers, both branches: relu(.) of the direct branch into Y, of the transposed one into Y2
-            st = launch_nc_fused(P, Y, Y2, sWs, (int)nz, d0, d1, d2, d3, ncn->wfused, ncn->b2, xmax, sWs, ncn->tile, stream);
+            st = launch_nc_fused(P, Y, Y2, sWs, (int)nz, d0, d1, d2, d3, ncn->wfused.dev<unsigned char>(), ncn->b2, xmax, sWs, ncn->tile, stream);
         }
         if (st != P2P_OK) return st;
         launch_maxima(Y, nAc, nBc, rkey2, ckey2, sWs, sWs, Y2, nz, stream);
@@ -180,7 +169,7 @@ extern "C" int p2p_neigh_consensus_batch(const float *x, int batch, int hA, int 
     P2P_HIP_CHECK(hipMemsetAsync(xmax, 0, (size_t)batch * sizeof(int), stream));
     const int st = launch_absmax(x, nel, nel, batch, xmax, 1, stream);
     if (st != P2P_OK) return st;
-    return launch_nc_fused(x, y_out, nullptr, nel, batch, hA, wA, hB, wB, ncn->wfused, ncn->b2, xmax, 1, ncn->tile, stream);
+    return launch_nc_fused(x, y_out, nullptr, nel, batch, hA, wA, hB, wB, ncn->wfused.dev<unsigned char>(), ncn->b2, xmax, 1, ncn->tile, stream);
 }
 
 extern "C" int p2p_delta_unpack(const uint8_t *delta, size_t n, int ksize, int64_t *out, p2p_stream_t stream) {

@@ -2,10 +2,12 @@
 // consensus_generic.hip, included by coarse.hip) and the host API over them (coarse_api.hip).  Every source that defines one of
 // these functions includes this header, so a prototype that drifts from its definition does not compile.
 #pragma once
-#include "p2p_common.h"
+#include "host_pack.h"
 #include <algorithm>
 
 namespace p2p {
+
+struct NcGen;
 
 // ---- coarse.hip: feature preparation, correlation + pooling, mutual matching (nz: pairs of the launch) -----------------------
 struct PrepArgs {
@@ -41,7 +43,7 @@ void launch_matches_topk(const MatchArgs &m, int batch, int topk, int do_softmax
 void launch_delta_unpack(const uint8_t *delta, size_t n, int k, long long *out, hipStream_t stream);
 
 // ---- consensus.hip: the fused kernel of the released stack --------------------------------------------------------------
-void pack_nc_fused(const float *w1, const float *b1, const float *w2, std::vector<unsigned char> &out);
+void pack_nc_fused(const float *w1, const float *b1, const float *w2, DeviceBlob &out);      // lays out and fills the staging copy
 int launch_nc_fused(const float *X, float *Y, float *Y2, size_t stride, int pairs, int d0, int d1, int d2, int d3,
                     const unsigned char *w_dev, float b2, const int *xmax, size_t xmax_stride, const int *forced_tile,
                     hipStream_t stream);
@@ -55,3 +57,12 @@ int launch_nc_generic(const NcGen &g, const float *X, size_t s_x, float *Y, size
                       int d0, int d1, int d2, int d3, hipStream_t stream);
 
 }  // namespace p2p
+
+// The opaque handle of include/p2p_hip.h: the fused kernel's weights or a generic stack.  `delete` frees either.
+struct p2p_ncn {
+    float b2;                // scalar bias of layer 2 (same for both branches)
+    p2p::DeviceBlob wfused;  // both layers, both branches as fp16x2 MFMA fragments (consensus.hip)
+    int tile[3];             // forced (ta, tb, tc) of the fused kernel, 0 = automatic (p2p_ncn_set_tile: tests and sweeps)
+    p2p::NcGen *gen;         // a generic handle (p2p_ncn_create_config): its layers; the fields above are unused then
+    ~p2p_ncn() { p2p::nc_generic_destroy(gen); }
+};

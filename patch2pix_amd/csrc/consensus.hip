@@ -570,31 +570,21 @@ __global__ __launch_bounds__(NCF_THREADS, 2) void nc_fused_kernel(NcFusedArgs a)
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-static uint16_t h_f2h(float v) { return __builtin_bit_cast(uint16_t, (_Float16)v); }
-static float h_h2f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
 static void put2(unsigned char *frag, int lane, int j, float v) {      // frag: [plane 2][lane 64][8 fp16]
     uint16_t *d = (uint16_t *)frag;
-    const uint16_t h0 = h_f2h(v);
-    d[lane * 8 + j] = h0;
-    d[(64 + lane) * 8 + j] = h_f2h(v - h_h2f(h0));
-}
-static int pow2_exponent_to(float mx, int target) {      // t with mx * 2^t in [2^(target-1), 2^target)
-    if (!(mx > 0.f) || !std::isfinite(mx)) return 0;
-    int e;
-    std::frexp(mx, &e);
-    return target - e;
+    split_fp16_planes(v, &d[lane * 8 + j], &d[(64 + lane) * 8 + j]);
 }
 
 // w1 / w2 in the reference's stored layout (conv4d.py:119-120): w1s[da][o][0][db][dc][dd], w2s[da][0][c][db][dc][dd]
-void pack_nc_fused(const float *w1, const float *b1, const float *w2, std::vector<unsigned char> &out) {
-    out.assign(2 * NCF_BRANCH_BYTES, 0);
+void pack_nc_fused(const float *w1, const float *b1, const float *w2, DeviceBlob &out) {
+    unsigned char *const bytes = out.at<unsigned char>(out.take<unsigned char>(2 * NCF_BRANCH_BYTES));
     auto W1 = [&](int o, int da, int db, int dc, int dd) { return w1[(((da * 16 + o) * 3 + db) * 3 + dc) * 3 + dd]; };
     auto W2 = [&](int c, int da, int db, int dc, int dd) { return w2[(((da * 16 + c) * 3 + db) * 3 + dc) * 3 + dd]; };
     for (int br = 0; br < 2; ++br) {
         // the transposed branch evaluates conv(x^T)^T: the same volume with A/B-swapped taps
         auto W1b = [&](int o, int da, int db, int dc, int dd) { return br ? W1(o, dc, dd, da, db) : W1(o, da, db, dc, dd); };
         auto W2b = [&](int c, int da, int db, int dc, int dd) { return br ? W2(c, dc, dd, da, db) : W2(c, da, db, dc, dd); };
-        unsigned char *base = out.data() + (size_t)br * NCF_BRANCH_BYTES;
+        unsigned char *base = bytes + (size_t)br * NCF_BRANCH_BYTES;
         int t1[16];
         float hmax = 0.f, w2max = 0.f;
         for (int o = 0; o < 16; ++o) {
@@ -719,14 +709,9 @@ int launch_nc_fused(const float *X, float *Y, float *Y2, size_t stride, int pair
     const size_t lds = nc_fused_lds_bytes(a.tb, a.tc, a.P);
     P2P_REQUIRE(a.P <= 64 && lds <= 160 * 1024 && a.tc + 4 <= 12 && (a.tc + 2) * a.P <= 512, P2P_EUNSUPPORTED,
                 "consensus tile does not fit (P %d, tc %d, LDS %zu)", a.P, a.tc, lds);
-    int dev = 0;
-    P2P_HIP_CHECK(hipGetDevice(&dev));
     static DeviceOnce attr_set;
-    if (!attr_set.done(dev)) {
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)nc_fused_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)nc_fused_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set.set(dev);
-    }
+    const int dev = raise_lds_limit(attr_set, {{(const void *)nc_fused_kernel<false>, 160 * 1024}, {(const void *)nc_fused_kernel<true>, 160 * 1024}});
+    if (dev < 0) return dev;
     if (a.tb == 5 && a.tc == 8 && a.td == 40 && a.P == 44)
         hipLaunchKernelGGL(nc_fused_kernel<true>, dim3(a.na * a.nb * a.nc * a.nd, 2, pairs), dim3(NCF_THREADS), lds, stream, a);
     else

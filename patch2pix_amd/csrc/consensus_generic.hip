@@ -17,6 +17,7 @@
 // The direct branch's last layer stores y, the transposed branch's last layer adds to it (plain read-add-write: one lane per
 // word, launches of one stream run in order).  Every output sums its K terms super-step by super-step, j = 0..3: the order
 // depends on the configuration alone -- not on the pair's position in the batch, the batch size or the workspace.
+// The handle (NcGen) holds every layer's fragments and biases in one DeviceBlob (host_pack.h).
 // Device code is restricted to what the kernel emulator of the test-suite runs.  Compiled as part of coarse.hip.
 #pragma once
 #include "coarse_common.h"
@@ -42,7 +43,7 @@ struct NcGenLayer {
 struct NcGen {
     int n_layers, symmetric, cpmax;
     NcGenLayer layer[NCG_MAX_LAYERS];
-    float *mem;              // one device allocation: every layer's fragments and biases
+    DeviceBlob mem;          // one device allocation: every layer's fragments and biases
 };
 
 struct NcGenArgs {
@@ -171,10 +172,10 @@ int nc_generic_create(const p2p_ncn_config *cfg, const p2p_ncn_tensors *t, NcGen
         P2P_REQUIRE(t->w[i] && t->b[i], P2P_EINVAL, "%s: null pointer among the tensors of layer %d", F, i);
 
     NcGen *g = new NcGen();
-    g->n_layers = cfg->n_layers; g->symmetric = cfg->symmetric != 0; g->cpmax = 0; g->mem = nullptr;
+    g->n_layers = cfg->n_layers; g->symmetric = cfg->symmetric != 0; g->cpmax = 0;
     const int nbr = g->symmetric ? 2 : 1;
-    size_t off = 0, o_w[NCG_MAX_LAYERS][2], o_b[NCG_MAX_LAYERS];
-    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~size_t(63); return o; };
+    size_t o_w[NCG_MAX_LAYERS][2], o_b[NCG_MAX_LAYERS];
+    auto take = [&](size_t n) { return g->mem.take<float>(n); };
     for (int i = 0; i < g->n_layers; ++i) {
         NcGenLayer &L = g->layer[i];
         const bool last = i + 1 == g->n_layers;
@@ -187,35 +188,29 @@ int nc_generic_create(const p2p_ncn_config *cfg, const p2p_ncn_tensors *t, NcGen
         for (int br = 0; br < nbr; ++br) o_w[i][br] = take((size_t)L.nsteps * 256);
         o_b[i] = take(16);
     }
-    std::vector<float> h(off, 0.f);
+    float *h = g->mem.at<float>(0);
     for (int i = 0; i < g->n_layers; ++i) {
         const NcGenLayer &L = g->layer[i];
         for (int br = 0; br < nbr; ++br) gen_nc_pack(t->w[i], L, i == 0, br, &h[o_w[i][br]]);
         for (int q = 0; q < L.co; ++q) h[o_b[i] + q] = t->b[i][q];
     }
-    hipError_t e = hipMalloc(&g->mem, h.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(g->mem, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        set_error("%s: uploading the packed consensus net failed: %s", F, hipGetErrorString(e));
-        if (g->mem) (void)hipFree(g->mem);
+    const int st = g->mem.upload("p2p_ncn_create_config: the packed consensus net");
+    if (st != P2P_OK) {
         delete g;
-        return P2P_EHIP;
+        return st;
     }
+    const float *mem = g->mem.dev<float>();
     for (int i = 0; i < g->n_layers; ++i) {
         NcGenLayer &L = g->layer[i];
-        L.w[0] = g->mem + o_w[i][0];
-        L.w[1] = g->symmetric ? g->mem + o_w[i][1] : nullptr;
-        L.bias = g->mem + o_b[i];
+        L.w[0] = mem + o_w[i][0];
+        L.w[1] = g->symmetric ? mem + o_w[i][1] : nullptr;
+        L.bias = mem + o_b[i];
     }
     *out = g;
     return P2P_OK;
 }
 
-void nc_generic_destroy(NcGen *g) {
-    if (!g) return;
-    if (g->mem) (void)hipFree(g->mem);
-    delete g;
-}
+void nc_generic_destroy(NcGen *g) { delete g; }      // (NcGen is complete in this unit only)
 
 // scratch of one volume: the two activation buffers layers alternate between (a single layer needs none: one block)
 size_t nc_generic_ws_bytes(const NcGen &g, size_t cells) {

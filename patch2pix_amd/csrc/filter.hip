@@ -7,7 +7,7 @@
 // item lives in LDS.  Longer lists (a 960x1280 pair has 9600 rows, a 1600-pixel image 15000) are sorted in a
 // caller-provided workspace: chunks of 8192 rows are sorted in LDS, the network steps whose stride spans chunks run on
 // global memory (the work-group's own stores, ordered by its barriers), the rest of every merge again chunk-wise in LDS.
-#include "p2p_common.h"
+#include "host_pack.h"
 
 namespace p2p {
 
@@ -282,16 +282,10 @@ extern "C" int p2p_filter_coarse_batch(const int64_t *matches, const float *scor
                 "p2p_filter_coarse: %d rows per item need a workspace of %zu bytes (p2p_filter_coarse_workspace_bytes), got %zu",
                 n, need, workspace ? workspace_bytes : (size_t)0);
     const size_t lds = big ? (size_t)FILTER_LDS_ROWS * 12 : (size_t)npad * 16;
-    int dev = 0;
-    P2P_HIP_CHECK(hipGetDevice(&dev));
     static DeviceOnce attr_set;      // per device: a process may drive several GPUs
-    if (!attr_set.done(dev)) {
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)filter_coarse_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          FILTER_LDS_ROWS * 16));
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)filter_coarse_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          FILTER_LDS_ROWS * 12));
-        attr_set.set(dev);
-    }
+    const int dev = raise_lds_limit(attr_set, {{(const void *)filter_coarse_kernel<false>, FILTER_LDS_ROWS * 16},
+                                               {(const void *)filter_coarse_kernel<true>, FILTER_LDS_ROWS * 12}});
+    if (dev < 0) return dev;
     FilterArgs a{(const long long *)matches, scores, n, npad, ncn_thres, mutual, (long long *)out_matches, out_scores, out_counts,
                  (unsigned char *)workspace};
     if (big) hipLaunchKernelGGL(filter_coarse_kernel<true>, dim3(batch), dim3(FT), lds, (hipStream_t)stream, a);

@@ -1,0 +1,143 @@
+// Host side of every handle, written once: the device allocation behind a handle's packed weights (DeviceBlob), the arithmetic
+// that goes into those blobs (BatchNorm fold, fp32 -> two fp16 planes, power-of-two channel exponents, FC weights as MFMA
+// fragments) and what every launcher with a large dynamic LDS allocation does once per device (raise_lds_limit).  Host code
+// only: included where weights are packed or such a kernel is launched, not from p2p_common.h.
+#pragma once
+#include "p2p_common.h"
+#include <algorithm>
+#include <cmath>
+#include <initializer_list>
+#include <utility>
+#include <vector>
+
+namespace p2p {
+
+// One device allocation made of aligned parts.  take() lays the parts out (all of them, before anything is filled in), at() is
+// the zero-filled host staging copy a packer writes, upload() is the one hipMalloc + hipMemcpy, dev() the device address of a
+// part afterwards.  The blob owns the allocation: a handle holds its blob(s) by value, so `delete handle` frees them.
+class DeviceBlob {
+public:
+    DeviceBlob() = default;
+    DeviceBlob(const DeviceBlob &) = delete;
+    DeviceBlob &operator=(const DeviceBlob &) = delete;
+    DeviceBlob(DeviceBlob &&o) noexcept : host_(std::move(o.host_)), dev_(o.dev_), bytes_(o.bytes_) { o.dev_ = nullptr; o.bytes_ = 0; }
+    DeviceBlob &operator=(DeviceBlob &&o) noexcept {
+        if (this != &o) {
+            release();
+            host_ = std::move(o.host_); dev_ = o.dev_; bytes_ = o.bytes_;
+            o.dev_ = nullptr; o.bytes_ = 0;
+        }
+        return *this;
+    }
+    ~DeviceBlob() { release(); }
+
+    // a part of `count` elements of T, padded to 64 elements (256 bytes for the fp32 parts); returns where it starts, in elements
+    // of T from the start of the blob
+    template <class T> size_t take(size_t count) {
+        const size_t off = bytes_ / sizeof(T);
+        bytes_ += ((count + 63) & ~size_t(63)) * sizeof(T);
+        return off;
+    }
+    size_t bytes() const { return bytes_; }
+    template <class T> T *at(size_t off) {                  // host staging copy (zeros until written), valid until upload()
+        if (host_.size() < bytes_) host_.resize(bytes_, 0);
+        return (T *)host_.data() + off;
+    }
+    template <class T> const T *dev(size_t off = 0) const { return (const T *)dev_ + off; }     // after upload()
+    bool uploaded() const { return dev_ != nullptr; }
+
+    // P2P_ENOMEM when the allocation fails, P2P_EHIP when the copy does (nothing stays allocated either way)
+    int upload(const char *what) {
+        at<unsigned char>(0);
+        hipError_t e = hipMalloc(&dev_, bytes_);
+        if (e != hipSuccess) {
+            dev_ = nullptr;
+            set_error("%s: hipMalloc of %zu bytes failed: %s", what, bytes_, hipGetErrorString(e));
+            return P2P_ENOMEM;
+        }
+        e = hipMemcpy(dev_, host_.data(), bytes_, hipMemcpyHostToDevice);
+        std::vector<unsigned char>().swap(host_);
+        if (e != hipSuccess) {
+            release();
+            set_error("%s: hipMemcpy of %zu bytes failed: %s", what, bytes_, hipGetErrorString(e));
+            return P2P_EHIP;
+        }
+        return P2P_OK;
+    }
+    void release() {                                        // harmless on a blob that was never uploaded, and twice
+        if (dev_) (void)hipFree(dev_);
+        dev_ = nullptr;
+    }
+
+private:
+    std::vector<unsigned char> host_;
+    unsigned char *dev_ = nullptr;
+    size_t bytes_ = 0;
+};
+
+// eval-mode BatchNorm (eps 1e-5) as y = x * scale + shift
+static inline void fold_bn(const p2p_bn_params &bn, int n, float *scale, float *shift) {
+    for (int i = 0; i < n; ++i) {
+        const float inv = 1.0f / std::sqrt(bn.running_var[i] + 1e-5f);
+        const float a = bn.weight[i] * inv;
+        scale[i] = a;
+        shift[i] = bn.bias[i] - bn.running_mean[i] * a;
+    }
+}
+
+// fp32 -> two fp16 planes: v = hi + lo to within 2^-24 |v| (both round to nearest even, like the kernels' own splits)
+static inline void split_fp16_planes(float v, uint16_t *hi, uint16_t *lo) {
+    const _Float16 h = (_Float16)v;
+    *hi = __builtin_bit_cast(uint16_t, h);
+    *lo = __builtin_bit_cast(uint16_t, (_Float16)(v - (float)h));
+}
+
+// the exponent t for which mx * 2^t lies in [2^(target-1), 2^target): with target 12 the exact scaling that brings a channel's
+// largest weight magnitude mx to the top of the fp16 range the planes resolve (undone in the folded BatchNorm scale); 0 for a
+// channel of zeros or with a non-finite weight
+static inline int pow2_exponent_to(double mx, int target) {
+    if (!(mx > 0.0) || !std::isfinite(mx)) return 0;
+    int e;
+    std::frexp(mx, &e);          // mx = m * 2^e, m in [0.5, 1)
+    return target - e;
+}
+
+// fc weight [n][k] (row-major, torch Linear; n, k multiples of 16) -> B fragments of v_mfma_f32_16x16x4_f32 in the K order of
+// fc_batch_parse / gen_fc_kernel: out[((S * (n / 16) + tile) * 64 + lane) * 4 + j] = W[16 tile + (lane & 15)][16 S + 4 (lane >> 4) + j]
+static inline void pack_fc_mfma(const float *w, int n, int k, float *out) {
+    for (int S = 0; S < k / 16; ++S)
+        for (int t = 0; t < n / 16; ++t)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int j = 0; j < 4; ++j)
+                    out[(((size_t)S * (n / 16) + t) * 64 + lane) * 4 + j] = w[(size_t)(16 * t + (lane & 15)) * k + 16 * S + 4 * (lane >> 4) + j];
+}
+
+// ---- launchers ------------------------------------------------------------------------------------------------------------
+// What a launcher does before a kernel whose dynamic LDS allocation exceeds the default limit: ask for the current device (once
+// per launch) and, on that device's first launch, raise the limit of each kernel; `once` is set only after all of them succeeded.
+// Returns the device (>= 0) or P2P_EHIP.
+struct LdsLimit { const void *kernel; int bytes; };
+static inline int raise_lds_limit(DeviceOnce &once, std::initializer_list<LdsLimit> kernels) {
+    int dev = 0;
+    P2P_HIP_CHECK(hipGetDevice(&dev));
+    if (!once.done(dev)) {
+        for (const LdsLimit &k : kernels) P2P_HIP_CHECK(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes));
+        once.set(dev);
+    }
+    return dev;
+}
+
+// compute units of a device (>= 1; the grids of the persistent kernels), asked once per device and process; P2P_EHIP (< 0) if the
+// runtime refuses
+static inline int device_cu_count(int dev) {
+    static std::atomic<int> cus[64];
+    const bool slot = dev >= 0 && dev < 64;
+    int ncu = slot ? cus[dev].load(std::memory_order_relaxed) : 0;
+    if (ncu > 0) return ncu;
+    P2P_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    ncu = std::max(ncu, 1);
+    if (slot) cus[dev].store(ncu, std::memory_order_relaxed);
+    return ncu;
+}
+
+}  // namespace p2p

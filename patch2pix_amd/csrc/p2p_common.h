@@ -126,12 +126,3 @@ static inline int check_launch(const char *what) {
 }
 
 }  // namespace p2p
-
-// opaque handles -------------------------------------------------------------------------------
-namespace p2p { struct NcGen; }      // consensus_generic.hip
-struct p2p_ncn {
-    float b2;                // scalar bias of layer 2 (same for both branches)
-    unsigned char *wfused;   // both layers, both branches as fp16x2 MFMA fragments (consensus.hip), one device allocation
-    int tile[3];             // forced (ta, tb, tc) of the fused kernel, 0 = automatic (p2p_ncn_set_tile: tests and sweeps)
-    p2p::NcGen *gen;         // a generic handle (p2p_ncn_create_config): its layers; the fields above are unused then
-};

@@ -349,14 +349,9 @@ void pack_f32_weights(const float *conv1_w, const float *conv2_w, float *wp1, fl
 
 // one work-group per proposal slot
 int launch_regress_f32(const RegressArgs &a, int n, hipStream_t stream) {
-    int dev = 0;
-    P2P_HIP_CHECK(hipGetDevice(&dev));
     static DeviceOnce attr_set;
-    if (!attr_set.done(dev)) {
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)regress_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)LDS_BYTES));
-        attr_set.set(dev);
-    }
+    const int dev = raise_lds_limit(attr_set, {{(const void *)regress_kernel, (int)LDS_BYTES}});
+    if (dev < 0) return dev;
     hipLaunchKernelGGL(regress_kernel, dim3(n), dim3(NT), LDS_BYTES, stream, a);
     return check_launch("regress_kernel");
 }

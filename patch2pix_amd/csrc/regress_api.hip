@@ -1,5 +1,5 @@
-// Fine stage, host side: the regressor handle (one RegDev view per arithmetic mode), mode selection, the p2p_regress* entry
-// points and the workspace queries of include/p2p_hip.h.  No kernel lives here: a mode is a row of MODES, whose launcher and
+// Fine stage, host side: the regressor handle (one RegDev view and one DeviceBlob, host_pack.h, per arithmetic mode, plus the blob
+// of the parameters every mode shares), mode selection, the p2p_regress* entry points and the workspace queries of include/p2p_hip.h.  No kernel lives here: a mode is a row of MODES, whose launcher and
 // packers sit next to their kernels (regress.hip, regress_h2.hip, regress_wino.hip; declared in regress_common.h).  Compiled
 // as part of api.hip, not as a unit of its own.
 #include "regress_common.h"
@@ -28,76 +28,51 @@ static int mode_index(int mode) {
     return -1;
 }
 
-static void fold_bn(const p2p_bn_params &bn, int n, float *scale, float *shift) {
-    for (int i = 0; i < n; ++i) {
-        const float inv = 1.0f / std::sqrt(bn.running_var[i] + 1e-5f);
-        const float a = bn.weight[i] * inv;
-        scale[i] = a;
-        shift[i] = bn.bias[i] - bn.running_mean[i] * a;
-    }
-}
-
-static int upload(const std::vector<float> &h, float **dev, const char *what) {
-    *dev = nullptr;
-    P2P_HIP_CHECK(hipMalloc(dev, h.size() * sizeof(float)));
-    hipError_t e = hipMemcpy(*dev, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(*dev);
-        *dev = nullptr;
-        set_error("hipMemcpy of %s failed: %s", what, hipGetErrorString(e));
-        return P2P_EHIP;
-    }
-    return P2P_OK;
-}
-
 // pack + upload the convolution weights in the stream order of `mode`'s kernels, complete the mode's view (once per handle and mode)
 static int ensure_mode(p2p_regressor *r, int mode) {
     const int m = mode_index(mode);
-    if (r->stream[m]) return P2P_OK;
-    // the parts of the mode's allocation: the RegDev pointer each becomes, at which float it starts
+    DeviceBlob &blob = r->stream[m];
+    if (blob.uploaded()) return P2P_OK;
+    // the parts of the mode's blob: the RegDev pointer each becomes, at which float it starts
     struct Part { const float *RegDev::*field; size_t off; };
     std::vector<Part> parts;
-    size_t total = 0;
+    DeviceBlob b;
     auto take = [&](const float *RegDev::*field, size_t floats) {
-        parts.push_back({field, total});
-        total += (floats + 63) & ~size_t(63);
+        parts.push_back({field, b.take<float>(floats)});
         return parts.back().off;
     };
     const float *c1 = r->conv1_w.data(), *c2 = r->conv2_w.data(), *bn1s = r->bn1s_host.data(), *bn2s = r->bn2s_host.data();
-    std::vector<float> h;
     std::vector<int> t1(512), t2(512);
     const char *what;
     // fp16 modes: conv1 accumulates 2^12 (activations) x 2^t1[n] (weights) x the true sum, conv2 2^t2[n] x (the per-proposal scale
     // of H, undone in the kernel) x the true sum: exact powers of two folded into the BatchNorm scales
     if (mode == P2P_REGRESS_F32) {
         const size_t o1 = take(&RegDev::wp1, WP1_FLOATS), o2 = take(&RegDev::wp2, WP2_FLOATS);
-        h.assign(total, 0.f);
-        pack_f32_weights(c1, c2, &h[o1], &h[o2]);
+        pack_f32_weights(c1, c2, b.at<float>(o1), b.at<float>(o2));
         what = "the f32 weight streams";
     } else if (mode == P2P_REGRESS_FP16X2) {
         const size_t o1 = take(&RegDev::wh1, WH1_FLOATS), o2 = take(&RegDev::wh2, WH2_FLOATS);
         const size_t ob1 = take(&RegDev::bn1s_h, 512), ob2 = take(&RegDev::bn2s_h, 512);
-        h.assign(total, 0.f);
-        pack_h2_weights(c1, c2, &h[o1], &h[o2], t1.data(), t2.data());
-        fold_exponent(bn1s, t1.data(), 12, &h[ob1]);
-        fold_exponent(bn2s, t2.data(), 0, &h[ob2]);
+        pack_h2_weights(c1, c2, b.at<float>(o1), b.at<float>(o2), t1.data(), t2.data());
+        fold_exponent(bn1s, t1.data(), 12, b.at<float>(ob1));
+        fold_exponent(bn2s, t2.data(), 0, b.at<float>(ob2));
         what = "the fp16x2 weight streams";
     } else {
         // conv2 as Winograd filter blocks + conv1's fp16x2 stream (the same stream the direct mode runs, packed here on its own:
         // the direct mode's conv2 stream -- 9.6 MB per regressor -- is neither packed nor uploaded for this mode)
         const size_t o2 = take(&RegDev::ww2, WW2_FLOATS), ob2 = take(&RegDev::bn2s_w, 512);
         const size_t o1 = take(&RegDev::wh1, WH1_FLOATS), ob1 = take(&RegDev::bn1s_h, 512);
-        h.assign(total, 0.f);
-        pack_wino_weights(c2, &h[o2], t2.data());
-        pack_h2_weights(c1, nullptr, &h[o1], nullptr, t1.data(), nullptr);
-        fold_exponent(bn1s, t1.data(), 12, &h[ob1]);
-        fold_exponent(bn2s, t2.data(), 0, &h[ob2]);
+        pack_wino_weights(c2, b.at<float>(o2), t2.data());
+        pack_h2_weights(c1, nullptr, b.at<float>(o1), nullptr, t1.data(), nullptr);
+        fold_exponent(bn1s, t1.data(), 12, b.at<float>(ob1));
+        fold_exponent(bn2s, t2.data(), 0, b.at<float>(ob2));
         what = "the Winograd filter blocks and conv1's stream";
     }
-    const int st = upload(h, &r->stream[m], what);
+    const int st = b.upload(what);
     if (st != P2P_OK) return st;
+    blob = std::move(b);
     r->view[m] = r->common;
-    for (const Part &q : parts) r->view[m].*q.field = r->stream[m] + q.off;
+    for (const Part &q : parts) r->view[m].*q.field = blob.dev<float>(q.off);
     return P2P_OK;
 }
 
@@ -133,15 +108,16 @@ extern "C" int p2p_regressor_create(const p2p_regressor_params *p, p2p_regressor
                                  p->bnf2.weight, p->bnf2.bias, p->bnf2.running_mean, p->bnf2.running_var};
     for (const float *q : need) P2P_REQUIRE(q, P2P_EINVAL, "p2p_regressor_create: null weight pointer");
 
-    // everything but the convolution weights (which are packed per arithmetic mode, ensure_mode): one device allocation
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~size_t(63); return o; };
+    // everything but the convolution weights (which are packed per arithmetic mode, ensure_mode): one blob
+    p2p_regressor *r = new p2p_regressor();      // value-initialised: no stream, every view empty
+    DeviceBlob &b = r->dev;
+    auto take = [&](size_t n) { return b.take<float>(n); };
     const size_t o_bn1s = take(512), o_bn1b = take(512), o_bn2s = take(512), o_bn2b = take(512);
     const size_t o_fc1t = take(512 * 512), o_fc1b = take(512), o_bnf1s = take(512), o_bnf1b = take(512);
     const size_t o_fc2t = take(256 * 512), o_fc2b = take(256), o_bnf2s = take(256), o_bnf2b = take(256);
     const size_t o_fc3 = take(5 * 256), o_fc3b = take(8);
     const size_t o_fc1p = take(512 * 512), o_fc2p = take(256 * 512);
-    std::vector<float> h(off, 0.f);
+    float *h = b.at<float>(0);
     fold_bn(p->bn1, 512, &h[o_bn1s], &h[o_bn1b]);
     fold_bn(p->bn2, 512, &h[o_bn2s], &h[o_bn2b]);
     fold_bn(p->bnf1, 512, &h[o_bnf1s], &h[o_bnf1b]);
@@ -151,35 +127,32 @@ extern "C" int p2p_regressor_create(const p2p_regressor_params *p, p2p_regressor
         for (int k = 0; k < 512; ++k) h[o_fc1t + ((size_t)(k / 4) * 512 + o) * 4 + (k & 3)] = p->fc1_w[(size_t)o * 512 + k];
     for (int o = 0; o < 256; ++o)
         for (int k = 0; k < 512; ++k) h[o_fc2t + ((size_t)(k / 4) * 256 + o) * 4 + (k & 3)] = p->fc2_w[(size_t)o * 512 + k];
-    pack_fc_mfma(p->fc1_w, 512, &h[o_fc1p]);      // the same two layers as MFMA fragments (batched tail of the fp16x2 kernel)
-    pack_fc_mfma(p->fc2_w, 256, &h[o_fc2p]);
+    pack_fc_mfma(p->fc1_w, 512, 512, &h[o_fc1p]);      // the same two layers as MFMA fragments (batched tail of the fp16x2 kernel)
+    pack_fc_mfma(p->fc2_w, 256, 512, &h[o_fc2p]);
     for (int i = 0; i < 512; ++i) h[o_fc1b + i] = p->fc1_b[i];
     for (int i = 0; i < 256; ++i) h[o_fc2b + i] = p->fc2_b[i];
     for (int i = 0; i < 5 * 256; ++i) h[o_fc3 + i] = p->fc3_w[i];
     for (int i = 0; i < 5; ++i) h[o_fc3b + i] = p->fc3_b[i];
-
-    p2p_regressor *r = new p2p_regressor();      // value-initialised: no stream, every view empty
-    int st = upload(h, &r->dev, "the regressor's BatchNorm / FC parameters");
-    if (st != P2P_OK) {
-        delete r;
-        return st;
-    }
-    (void)hipGetDevice(&r->device);
     r->conv1_w.assign(p->conv1_w, p->conv1_w + (size_t)512 * 518 * 9);      // host copies: another mode's stream is packed on demand
     r->conv2_w.assign(p->conv2_w, p->conv2_w + (size_t)512 * 512 * 9);
     r->bn1s_host.assign(&h[o_bn1s], &h[o_bn1s] + 512);
     r->bn2s_host.assign(&h[o_bn2s], &h[o_bn2s] + 512);
-    RegDev &c = r->common;
-    const float *dev = r->dev;
-    c.bn1s = dev + o_bn1s; c.bn1b = dev + o_bn1b; c.bn2s = dev + o_bn2s; c.bn2b = dev + o_bn2b;
-    c.fc1t = dev + o_fc1t; c.fc1b = dev + o_fc1b; c.bnf1s = dev + o_bnf1s; c.bnf1b = dev + o_bnf1b;
-    c.fc2t = dev + o_fc2t; c.fc2b = dev + o_fc2b; c.bnf2s = dev + o_bnf2s; c.bnf2b = dev + o_bnf2b;
-    c.fc3 = dev + o_fc3; c.fc3b = dev + o_fc3b;
-    c.fc1p = dev + o_fc1p; c.fc2p = dev + o_fc2p;
-    r->mode = P2P_REGRESS_DEFAULT;
-    st = ensure_mode(r, r->mode);
+
+    int st = b.upload("the regressor's BatchNorm / FC parameters");
+    if (st == P2P_OK) {
+        (void)hipGetDevice(&r->device);
+        RegDev &c = r->common;
+        const float *dev = b.dev<float>();
+        c.bn1s = dev + o_bn1s; c.bn1b = dev + o_bn1b; c.bn2s = dev + o_bn2s; c.bn2b = dev + o_bn2b;
+        c.fc1t = dev + o_fc1t; c.fc1b = dev + o_fc1b; c.bnf1s = dev + o_bnf1s; c.bnf1b = dev + o_bnf1b;
+        c.fc2t = dev + o_fc2t; c.fc2b = dev + o_fc2b; c.bnf2s = dev + o_bnf2s; c.bnf2b = dev + o_bnf2b;
+        c.fc3 = dev + o_fc3; c.fc3b = dev + o_fc3b;
+        c.fc1p = dev + o_fc1p; c.fc2p = dev + o_fc2p;
+        r->mode = P2P_REGRESS_DEFAULT;
+        st = ensure_mode(r, r->mode);
+    }
     if (st != P2P_OK) {
-        p2p_regressor_destroy(r);
+        delete r;
         return st;
     }
     *out = r;
@@ -199,14 +172,7 @@ extern "C" int p2p_regressor_create_config(const p2p_regressor_config *config, c
     return P2P_OK;
 }
 
-extern "C" void p2p_regressor_destroy(p2p_regressor *reg) {
-    if (!reg) return;
-    regressor_generic_destroy(reg->gen);
-    (void)hipFree(reg->dev);
-    for (float *s : reg->stream)
-        if (s) (void)hipFree(s);
-    delete reg;
-}
+extern "C" void p2p_regressor_destroy(p2p_regressor *reg) { delete reg; }
 
 // counts: per item, the number of slots in the concatenated arrays (host memory); dev_counts (optional, device
 // memory, indexed like counts): how many of those slots hold a proposal -- the remaining work-groups exit at once.

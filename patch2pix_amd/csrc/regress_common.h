@@ -1,7 +1,7 @@
 // Pieces shared by the fine-stage sources: the kernels (exact-f32 MFMA, regress.hip; fp16x2, regress_h2.hip / regress_wino.hip),
 // each with its weight packer and its launcher, and the host API over them (regress_api.hip: the handle, the modes, the C ABI).
 #pragma once
-#include "p2p_common.h"
+#include "host_pack.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -337,47 +337,14 @@ __device__ __forceinline__ void fc_batch_parse(const RegDev &R, const RegressArg
     }
 }
 
-// fc weight [N][512] (row-major, torch Linear) -> B fragments of v_mfma_f32_16x16x4_f32 in the K order of fc_batch_parse:
-// out[((S * (N / 16) + tile) * 64 + lane) * 4 + j] = W[16 tile + (lane & 15)][16 S + 4 (lane >> 4) + j]
-static inline void pack_fc_mfma(const float *w, int N, float *out) {
-    for (int S = 0; S < 32; ++S)
-        for (int t = 0; t < N / 16; ++t)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 4; ++j)
-                    out[(((size_t)S * (N / 16) + t) * 64 + lane) * 4 + j] = w[(size_t)(16 * t + (lane & 15)) * 512 + 16 * S + 4 * (lane >> 4) + j];
-}
-
 // ---- host side: what the weight packers share --------------------------------------------------------------------
-// fp32 -> two fp16 planes: v = hi + lo to within 2^-24 |v| (both round to nearest even, like the kernels' own splits)
-static inline void split_fp16_planes(float v, uint16_t *hi, uint16_t *lo) {
-    const _Float16 h = (_Float16)v;
-    *hi = __builtin_bit_cast(uint16_t, h);
-    *lo = __builtin_bit_cast(uint16_t, (_Float16)(v - (float)h));
-}
-// the exponent t for which 2^t brings a channel's largest weight magnitude mx into [2^11, 2^12) (exact scaling; undone in the
-// folded BatchNorm scale, fold_exponent); 0 for a channel of zeros or with a non-finite weight
-static inline int plane_exponent(double mx) {
-    if (!(mx > 0.0) || !std::isfinite(mx)) return 0;
-    int e;
-    std::frexp(mx, &e);          // mx = m * 2^e, m in [0.5, 1)
-    return 12 - e;
-}
+// the exponent that brings a channel's largest weight magnitude mx into [2^11, 2^12) (undone in the folded BatchNorm scale,
+// fold_exponent)
+static inline int plane_exponent(double mx) { return pow2_exponent_to(mx, 12); }
 // out[n] = bn_scale[n] * 2^-(bias + t[n]): a convolution whose weights carried 2^t[n] (and whose activations 2^bias)
 // accumulates 2^(bias + t[n]) x the true sum
 static inline void fold_exponent(const float *bn_scale, const int *t, int bias, float *out) {
     for (int n = 0; n < 512; ++n) out[n] = std::ldexp(bn_scale[n], -bias - t[n]);
-}
-// compute units of a device (>= 1; the grids of the persistent kernels), asked once per device and process; P2P_EHIP (< 0) if the
-// runtime refuses
-static inline int device_cu_count(int dev) {
-    static std::atomic<int> cus[64];
-    const bool slot = dev >= 0 && dev < 64;
-    int ncu = slot ? cus[dev].load(std::memory_order_relaxed) : 0;
-    if (ncu > 0) return ncu;
-    P2P_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    ncu = std::max(ncu, 1);
-    if (slot) cus[dev].store(ncu, std::memory_order_relaxed);
-    return ncu;
 }
 
 // ---- per source: stream sizes, packer (host), launcher ------------------------------------------------------------
@@ -444,7 +411,7 @@ struct GenNet {                          // one regressor as its kernels see it
 struct GenReg {
     p2p_regressor_config cfg;            // normalised: entries past n_feat / n_conv / n_fc are zero
     GenNet net;
-    float *mem;                          // one device allocation: packed weights, folds, biases
+    DeviceBlob mem;                      // one device allocation: packed weights, folds, biases
     // workspace of a chunk of U proposals (floats per proposal): mid matches 4, V fc_in, two FC buffers fc_max each, the
     // activation buffers a layer reads (act_a: even layers' input) and writes (act_b) -- offsets are these times U
     size_t fc_max, act_a, act_b, per_prop;
@@ -457,7 +424,6 @@ static inline size_t gen_ws_act(const GenReg &g, size_t U, int which) {
     return (4 + g.net.fc_in + 2 * g.fc_max + (which ? g.net.spp * g.act_a : 0)) * U;
 }
 int regressor_generic_create(const p2p_regressor_config *cfg, const p2p_regressor_tensors *t, GenReg **out);
-void regressor_generic_destroy(GenReg *g);
 // slots [0, n) of the launch described by `a` through reg1 (and reg2 on its un-truncated output when given), chunk by chunk
 int launch_regress_generic(const GenReg &reg1, const GenReg *reg2, const RegressArgs &a, int n, size_t workspace_bytes,
                            hipStream_t stream);
@@ -475,16 +441,17 @@ __device__ __forceinline__ float regress_parse_one(float s, int o, float base, c
 }  // namespace p2p
 
 // The opaque handle of include/p2p_hip.h.  A mode's kernels see the regressor through ONE RegDev: `common` (the BatchNorm / FC
-// pointers into `dev`, every stream pointer null) plus the stream pointers of that mode's own allocation.
+// pointers into `dev`, every stream pointer null) plus the stream pointers of that mode's own blob.  `delete` frees everything.
 constexpr int P2P_REGRESS_NMODES = 3;
 struct p2p_regressor {
-    int device;        // the device the handle was created on: every later allocation (another mode's weight stream) goes there
-    int mode;          // P2P_REGRESS_F32 | P2P_REGRESS_FP16X2 | P2P_REGRESS_FP16X2W (tuned handles), P2P_REGRESS_GENERIC (generic ones)
-    float *dev;        // BatchNorm folds + FC layers (every mode)
-    float *stream[P2P_REGRESS_NMODES];      // a mode's convolution weights in its kernels' stream order (+ the BatchNorm scales with
-                                            // its exponents folded in); packed on the mode's first selection, null until then
+    int device = 0;    // the device the handle was created on: every later allocation (another mode's weight stream) goes there
+    int mode = 0;      // P2P_REGRESS_F32 | P2P_REGRESS_FP16X2 | P2P_REGRESS_FP16X2W (tuned handles), P2P_REGRESS_GENERIC (generic ones)
+    p2p::DeviceBlob dev;                            // BatchNorm folds + FC layers (every mode)
+    p2p::DeviceBlob stream[P2P_REGRESS_NMODES];     // a mode's convolution weights in its kernels' stream order (+ the BatchNorm scales with
+                                                    // its exponents folded in); packed and uploaded on the mode's first selection
     std::vector<float> conv1_w, conv2_w, bn1s_host, bn2s_host;   // host copies the packings are built from
-    p2p::RegDev common, view[P2P_REGRESS_NMODES];
-    p2p::GenReg *gen;  // a generic handle (p2p_regressor_create_config; mode P2P_REGRESS_GENERIC): everything above but `device`
-                       // and `mode` is unused; null for a tuned handle
+    p2p::RegDev common{}, view[P2P_REGRESS_NMODES]{};
+    p2p::GenReg *gen = nullptr;      // a generic handle (p2p_regressor_create_config; mode P2P_REGRESS_GENERIC): everything above but
+                                     // `device` and `mode` is unused; null for a tuned handle
+    ~p2p_regressor() { delete gen; }
 };

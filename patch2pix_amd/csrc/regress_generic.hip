@@ -2,6 +2,7 @@
 // (p2p_regressor_config), exact fp32 on the matrix cores.  The tuned kernels (regress.hip, regress_h2.hip, regress_wino.hip) are
 // built around 518 / 512 channels and the 8x8 map; this file trades their fusion for generality: a chunk of proposals goes
 // through the network layer by layer, one launch per layer, activations in the caller's workspace (layout: regress_common.h).
+// The handle (GenReg) holds every packed weight, fold and bias in one DeviceBlob (host_pack.h).
 // Device code is restricted to what the kernel emulator of the test-suite runs: the two fp32 MFMA shapes, __shfl_xor,
 // atomicMax on int.  Compiled as part of api.hip (through regress_api.hip), not as a unit of its own.
 #include "regress_common.h"
@@ -259,23 +260,6 @@ static void gen_pack_conv(const float *w, int co, int cin, int ci_pad, int ker, 
                         out[dst] = (n < co && chn < cin) ? w[((size_t)n * cin + chn) * taps + tap] : 0.f;
                     }
 }
-// fc weight [n][k] -> B fragments in the K order of gen_fc_kernel (pack_fc_mfma for any k)
-static void gen_pack_fc(const float *w, int n, int k, float *out) {
-    for (int S = 0; S < k / 16; ++S)
-        for (int t = 0; t < n / 16; ++t)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 4; ++j)
-                    out[(((size_t)S * (n / 16) + t) * 64 + lane) * 4 + j] =
-                        w[(size_t)(16 * t + (lane & 15)) * k + 16 * S + 4 * (lane >> 4) + j];
-}
-static void gen_fold_bn(const p2p_bn_params &bn, int n, float *scale, float *shift) {      // eps 1e-5, as fold_bn
-    for (int i = 0; i < n; ++i) {
-        const float inv = 1.0f / std::sqrt(bn.running_var[i] + 1e-5f);
-        const float s = bn.weight[i] * inv;
-        scale[i] = s;
-        shift[i] = bn.bias[i] - bn.running_mean[i] * s;
-    }
-}
 static bool gen_bn_null(const p2p_bn_params &bn) { return !bn.weight || !bn.bias || !bn.running_mean || !bn.running_var; }
 
 int regressor_generic_create(const p2p_regressor_config *cfg, const p2p_regressor_tensors *t, GenReg **out) {
@@ -339,9 +323,8 @@ int regressor_generic_create(const p2p_regressor_config *cfg, const p2p_regresso
     N.post = post; N.feat_dim = feat_dim; N.spp = post ? 2 : 1;
     N.n_conv = cfg->n_conv; N.n_fc = cfg->n_fc;
     N.fc_in = (post ? 2 : 1) * cfg->conv_dim[cfg->n_conv - 1];
-    // one allocation: per conv layer weights / scale / shift, per FC layer weights / bias / scale / shift, the final Linear
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~size_t(63); return o; };
+    // one blob: per conv layer weights / scale / shift, per FC layer weights / bias / scale / shift, the final Linear
+    auto take = [&](size_t n) { return g->mem.take<float>(n); };
     size_t o_cw[4], o_cs[4], o_cb[4], o_fw[4], o_fb[4], o_fs[4], o_fh[4];
     const int cin0 = post ? feat_dim : 2 * feat_dim;
     int cin = cin0, hw = 16;
@@ -372,47 +355,38 @@ int regressor_generic_create(const p2p_regressor_config *cfg, const p2p_regresso
     const size_t o_ow = take((size_t)5 * k), o_ob = take(8);
     g->per_prop = 4 + N.fc_in + 2 * g->fc_max + N.spp * (g->act_a + g->act_b);
 
-    std::vector<float> h(off, 0.f);
+    float *h = g->mem.at<float>(0);
     cin = cin0;
     for (int i = 0; i < cfg->n_conv; ++i) {
         const GenConv &L = N.conv[i];
         gen_pack_conv(t->conv_w[i], L.co, cin, L.ci, L.ker, L.ntiles, &h[o_cw[i]]);
-        gen_fold_bn(t->conv_bn[i], L.co, &h[o_cs[i]], &h[o_cb[i]]);
+        fold_bn(t->conv_bn[i], L.co, &h[o_cs[i]], &h[o_cb[i]]);
         cin = L.co;
     }
     for (int i = 0; i < cfg->n_fc; ++i) {
         const GenFc &L = N.fc[i];
-        gen_pack_fc(t->fc_w[i], L.n, L.k, &h[o_fw[i]]);
+        pack_fc_mfma(t->fc_w[i], L.n, L.k, &h[o_fw[i]]);
         for (int q = 0; q < L.n; ++q) h[o_fb[i] + q] = t->fc_b[i][q];
-        gen_fold_bn(t->fc_bn[i], L.n, &h[o_fs[i]], &h[o_fh[i]]);
+        fold_bn(t->fc_bn[i], L.n, &h[o_fs[i]], &h[o_fh[i]]);
     }
     for (int q = 0; q < 5 * k; ++q) h[o_ow + q] = t->out_w[q];
     for (int q = 0; q < 5; ++q) h[o_ob + q] = t->out_b[q];
 
-    g->mem = nullptr;
-    hipError_t e = hipMalloc(&g->mem, h.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(g->mem, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        set_error("%s: uploading the packed regressor failed: %s", F, hipGetErrorString(e));
-        if (g->mem) (void)hipFree(g->mem);
+    const int st = g->mem.upload("p2p_regressor_create_config: the packed regressor");
+    if (st != P2P_OK) {
         delete g;
-        return P2P_EHIP;
+        return st;
     }
+    const float *mem = g->mem.dev<float>();
     for (int i = 0; i < cfg->n_conv; ++i) {
-        N.conv[i].w = g->mem + o_cw[i]; N.conv[i].scale = g->mem + o_cs[i]; N.conv[i].shift = g->mem + o_cb[i];
+        N.conv[i].w = mem + o_cw[i]; N.conv[i].scale = mem + o_cs[i]; N.conv[i].shift = mem + o_cb[i];
     }
     for (int i = 0; i < cfg->n_fc; ++i) {
-        N.fc[i].w = g->mem + o_fw[i]; N.fc[i].bias = g->mem + o_fb[i]; N.fc[i].scale = g->mem + o_fs[i]; N.fc[i].shift = g->mem + o_fh[i];
+        N.fc[i].w = mem + o_fw[i]; N.fc[i].bias = mem + o_fb[i]; N.fc[i].scale = mem + o_fs[i]; N.fc[i].shift = mem + o_fh[i];
     }
-    N.out_w = g->mem + o_ow; N.out_b = g->mem + o_ob;
+    N.out_w = mem + o_ow; N.out_b = mem + o_ob;
     *out = g;
     return P2P_OK;
-}
-
-void regressor_generic_destroy(GenReg *g) {
-    if (!g) return;
-    if (g->mem) (void)hipFree(g->mem);
-    delete g;
 }
 
 // one level of one chunk: gather, the conv stack, the FC tail, the outputs

@@ -1210,16 +1210,9 @@ void pack_h2_weights(const float *conv1_w, const float *conv2_w, float *wx1, flo
 }
 
 static int launch_h2(const RegressArgs &a, int n, bool wino, hipStream_t stream) {
-    int dev = 0;
-    P2P_HIP_CHECK(hipGetDevice(&dev));
     static DeviceOnce attr_set;
-    if (!attr_set.done(dev)) {
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)regress_h2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)XSM_BYTES));
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)regress_h2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)XSM_BYTES));
-        attr_set.set(dev);
-    }
+    const int dev = raise_lds_limit(attr_set, {{(const void *)regress_h2_kernel<false>, (int)XSM_BYTES}, {(const void *)regress_h2_kernel<true>, (int)XSM_BYTES}});
+    if (dev < 0) return dev;
     const int ncu_dev = device_cu_count(dev);
     if (ncu_dev < 0) return ncu_dev;
     // persistent work-groups: one fits a compute unit (LDS), each walks its share of the proposals

@@ -266,14 +266,9 @@ void pack_wino_weights(const float *conv2_w, float *out, int *t2) {
 // GEMMs (U -> V); then the level's FC tail, whose matches are the next level's proposals.
 int launch_regress_wino(const RegressArgs &args, int n, hipStream_t stream) {
     RegressArgs a = args;      // the level and the chunk of a launch are filled in below
-    int dev = 0;
-    P2P_HIP_CHECK(hipGetDevice(&dev));
     static DeviceOnce attr_set;
-    if (!attr_set.done(dev)) {
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)wino_gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WLDS));
-        P2P_HIP_CHECK(hipFuncSetAttribute((const void *)regress_fc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FC_LDS_BYTES));
-        attr_set.set(dev);
-    }
+    const int dev = raise_lds_limit(attr_set, {{(const void *)wino_gemm_kernel, (int)WLDS}, {(const void *)regress_fc_kernel, (int)FC_LDS_BYTES}});
+    if (dev < 0) return dev;
     const int ncu = device_cu_count(dev);
     if (ncu < 0) return ncu;
     P2P_REQUIRE(a.ws, P2P_EINVAL, "%s: the scratch buffer is missing", "launch_regress_wino");

@@ -71,7 +71,7 @@ void launch(dim3 grid, dim3 block, size_t lds_bytes, const std::function<void()>
 
 // ---- host API subset used by the library
 typedef int hipError_t;
-enum { hipSuccess = 0, hipErrorUnknown = 999 };
+enum { hipSuccess = 0, hipErrorOutOfMemory = 2, hipErrorUnknown = 999 };
 typedef struct hipemu_stream *hipStream_t;
 enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3 };
 enum hipFuncAttribute { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
@@ -88,7 +88,9 @@ static inline hipError_t hipGetLastError() { return hipSuccess; }
 static inline hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
 static inline hipError_t hipSetDevice(int) { return hipSuccess; }
 static inline hipError_t hipFuncSetAttribute(const void *, hipFuncAttribute, int) { return hipSuccess; }
+namespace hipemu { inline int refuse_allocs = 0; }      // tests: the next so many hipMalloc calls of this binary fail (0: none do)
 template <class T> static inline hipError_t hipMalloc(T **p, size_t n) {
+    if (hipemu::refuse_allocs > 0) { --hipemu::refuse_allocs; *p = nullptr; return hipErrorOutOfMemory; }
     *p = (T *)aligned_alloc(256, (n + 255) & ~size_t(255));
     return *p ? hipSuccess : hipErrorUnknown;
 }
