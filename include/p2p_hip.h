@@ -252,6 +252,37 @@ int p2p_coarse_matches_topk_batch(const float *corr4d, const uint8_t *delta, int
                                   int ksize, int upsample, int center, int topk, int do_softmax,
                                   int64_t *matches_out, float *scores_out, p2p_stream_t stream);
 
+/* Patch2Pix.cal_coarse_score -- reference networks/patch2pix.py:320-338 (since version 108): the NCNet pair score, the mean
+ * over all cells of both images of the best normalised consensus value, per pair.  With X[b] the volume of pair b as an
+ * [nA][nB] matrix (nA = hA*wA, nB = hB*wB, the dims of corr4d as given) and N the normalisation taken along the axis the
+ * maximum runs over:
+ *   column scores  sB[b][c] = max_a N_a(X[b][a][c])      row scores  sA[b][r] = max_c N_c(X[b][r][c])
+ *   cell_scores [B, nA + nB] fp32 = sA then sB per pair, the order of the reference's torch.cat([scores_A, scores_B]);
+ *                              optional (NULL: the cell scores pass through `workspace`)
+ *   pair_scores [B] fp32     = the mean of the pair's nA + nB cell scores; required.  The reference's scalar is the mean of
+ *                              these B values (every pair of a batch has the same cell count).
+ *   P2P_SCORE_NONE     N = identity: the maximum itself, bit for bit (`normalize=None`)
+ *   P2P_SCORE_SOFTMAX  1 / sum expf(x - max), the sum taken over the same slices in the same order as p2p_coarse_matches_batch
+ *                      takes it: a cell's score is the score that call returns for the cell, bit for bit
+ *   P2P_SCORE_L1       max(x / (sum x + 0.0001)).  A correctly rounded division is monotone, so this is max(x) / d for
+ *                      d = sum x + 0.0001 > 0 and min(x) / d for d < 0: maximum, minimum and sum come from one scan, then one
+ *                      IEEE division.  The volume need not be non-negative; d == 0 gives what IEEE gives.
+ * Summation and order: a pair's nA + nB cell scores are added in an order that (nA, nB) alone fixes -- thread t of one
+ * 256-thread work-group per pair adds cells t, t + 256, ... ascending, a wave its 64 partial sums in an xor tree, then the four
+ * waves ascending; no float atomics.  It depends neither on B, nor on the pair's slot in the batch, nor on the launch shape: a
+ * pair's cell and pair scores are bit-identical alone and in any batch.
+ * workspace: device memory, 4-byte aligned, p2p_coarse_score_workspace_bytes bytes (B x (nA + nB) floats), needed only when
+ * cell_scores is NULL (P2P_ENOMEM if it is missing or too small); ignored otherwise (NULL, 0 allowed).  Null corr4d or
+ * pair_scores, batch outside 1..65535, non-positive dims and an unknown normalisation -> P2P_EINVAL; all before the device is
+ * touched.  Two launches (csrc/score.hip), asynchronous on `stream`.  The query returns 0 for bad arguments. */
+#define P2P_SCORE_NONE    0
+#define P2P_SCORE_SOFTMAX 1
+#define P2P_SCORE_L1      2
+size_t p2p_coarse_score_workspace_bytes(int batch, int hA, int wA, int hB, int wB);
+int p2p_coarse_score_batch(const float *corr4d, int batch, int hA, int wA, int hB, int wB, int normalize,
+                           float *cell_scores, float *pair_scores, void *workspace, size_t workspace_bytes,
+                           p2p_stream_t stream);
+
 /* filter_coarse -- reference networks/utils.py:38-72 without the `ptmax` sampling (which draws from the host's numpy
  * RNG and therefore stays on the host): per batch item the lexicographically sorted distinct rows of matches [n,4]
  * with the score of their first occurrence; `mutual` keeps rows that occur more than once; an empty selection leaves

@@ -122,6 +122,11 @@ p2p_coarse_matches_batch = _sig("p2p_coarse_matches_batch", ctypes.c_int,
 p2p_coarse_matches_topk_batch = _sig("p2p_coarse_matches_topk_batch", ctypes.c_int,
                                      [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 10 +
                                      [ctypes.c_void_p, ctypes.c_void_p, c_stream])
+p2p_coarse_score_workspace_bytes = _sig("p2p_coarse_score_workspace_bytes", ctypes.c_size_t, [ctypes.c_int] * 5)
+p2p_coarse_score_batch = _sig("p2p_coarse_score_batch", ctypes.c_int,
+                              [ctypes.c_void_p] + [ctypes.c_int] * 6 +
+                              [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_stream])
+SCORE_NORMS = {None: 0, "softmax": 1, "l1": 2}          # P2P_SCORE_NONE / _SOFTMAX / _L1
 p2p_filter_coarse_workspace_bytes = _sig("p2p_filter_coarse_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int])
 p2p_filter_coarse_batch = _sig("p2p_filter_coarse_batch", ctypes.c_int,
                                [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
@@ -177,7 +182,8 @@ EXPORTS = ["p2p_version", "p2p_last_error", "p2p_ncn_create", "p2p_ncn_destroy",
            "p2p_regressor_get_mode", "p2p_conv_create", "p2p_conv_destroy", "p2p_conv_set_tile", "p2p_conv_forward", "p2p_absmax_batch", "p2p_stem_create", "p2p_stem_destroy", "p2p_stem_forward",
            "p2p_maxpool_nhwc", "p2p_nhwc_to_nchw", "p2p_regressor_create_config", "p2p_regress_workspace_bytes_for",
            "p2p_coarse_matches_topk_batch", "p2p_ncn_create_config", "p2p_ncn_is_generic", "p2p_coarse_workspace_bytes_for",
-           "p2p_neigh_consensus_workspace_bytes", "p2p_resize_workspace_bytes", "p2p_resize_bicubic_batch"]
+           "p2p_neigh_consensus_workspace_bytes", "p2p_resize_workspace_bytes", "p2p_resize_bicubic_batch",
+           "p2p_coarse_score_workspace_bytes", "p2p_coarse_score_batch"]
 
 
 def check(status, what):

@@ -23,7 +23,8 @@
 // fill 256 CUs in the consensus layers).
 //
 // This file: sections 1-3, each kernel with its launcher.  4, the neighbourhood consensus (ncn/model.py:145-155; conv4d.py:12-74):
-// consensus.hip (the released stack, one fused kernel) and consensus_generic.hip (any other); 5, matches.hip; host API: coarse_api.hip.
+// consensus.hip (the released stack, one fused kernel) and consensus_generic.hip (any other); 5, matches.hip; 6, the pair score
+// (patch2pix.py:320-338): score.hip; host API: coarse_api.hip.
 #include "coarse_common.h"
 
 namespace p2p {
@@ -552,6 +553,7 @@ void launch_mm_apply(const float *X, int nA, int nB, const int *rkey, const int 
 
 }  // namespace p2p
 
-// sections 4 (its shape-generic part) and 5: no units of their own
+// sections 4 (its shape-generic part), 5 and 6: no units of their own
 #include "consensus_generic.hip"
 #include "matches.hip"
+#include "score.hip"

@@ -1,6 +1,6 @@
 // Coarse stage, host side: the p2p_ncn handle (the fused kernel's packed weights in a DeviceBlob, host_pack.h, or a generic stack), the carve-up of the caller's
 // workspace, and the p2p_coarse_* / p2p_neigh_consensus_* / p2p_delta_unpack entry points of include/p2p_hip.h.  No kernel lives
-// here and none is launched from here: every kernel sits next to its launcher (coarse.hip, matches.hip, consensus.hip,
+// here and none is launched from here: every kernel sits next to its launcher (coarse.hip, matches.hip, score.hip, consensus.hip,
 // consensus_generic.hip; declared in coarse_common.h).  Compiled as part of api.hip, not as a unit of its own.
 #include "coarse_common.h"
 
@@ -214,6 +214,32 @@ extern "C" int p2p_coarse_matches_topk_batch(const float *corr4d, const uint8_t 
                 (size_t)nA * nB, (size_t)topk * ((size_t)nA + nB)};
     launch_matches_topk(m, batch, topk, do_softmax ? 1 : 0, (hipStream_t)stream);
     return check_launch("top-k match kernels");
+}
+
+extern "C" size_t p2p_coarse_score_workspace_bytes(int batch, int hA, int wA, int hB, int wB) {
+    if (batch < 1 || batch > 65535 || hA <= 0 || wA <= 0 || hB <= 0 || wB <= 0) return 0;
+    return (size_t)batch * ((size_t)hA * wA + (size_t)hB * wB) * sizeof(float);
+}
+
+extern "C" int p2p_coarse_score_batch(const float *corr4d, int batch, int hA, int wA, int hB, int wB, int normalize,
+                                      float *cell_scores, float *pair_scores, void *workspace, size_t workspace_bytes,
+                                      p2p_stream_t stream) {
+    P2P_REQUIRE(corr4d && pair_scores, P2P_EINVAL, "p2p_coarse_score: null argument");
+    P2P_REQUIRE(batch >= 1 && batch <= 65535, P2P_EINVAL, "p2p_coarse_score: batch %d out of range", batch);
+    P2P_REQUIRE(hA > 0 && wA > 0 && hB > 0 && wB > 0, P2P_EINVAL, "p2p_coarse_score: bad sizes");
+    const long long nA = (long long)hA * wA, nB = (long long)hB * wB;
+    P2P_REQUIRE(nA + nB < (1ll << 30), P2P_EINVAL, "p2p_coarse_score: bad sizes (%lld + %lld cells)", nA, nB);
+    P2P_REQUIRE(normalize == P2P_SCORE_NONE || normalize == P2P_SCORE_SOFTMAX || normalize == P2P_SCORE_L1, P2P_EINVAL,
+                "p2p_coarse_score: unknown normalisation %d", normalize);
+    if (!cell_scores) {      // the cell scores wait in the caller's scratch for the pair kernel
+        const size_t need = p2p_coarse_score_workspace_bytes(batch, hA, wA, hB, wB);
+        P2P_REQUIRE(workspace && workspace_bytes >= need, P2P_ENOMEM, "p2p_coarse_score: workspace of %zu bytes needed without cell_scores",
+                    need);
+        P2P_REQUIRE(((uintptr_t)workspace & 3) == 0, P2P_EINVAL, "p2p_coarse_score: the workspace must be 4-byte aligned");
+        cell_scores = (float *)workspace;
+    }
+    launch_score(ScoreArgs{corr4d, cell_scores, pair_scores, (int)nA, (int)nB, (size_t)(nA * nB)}, batch, normalize, (hipStream_t)stream);
+    return check_launch("score kernels");
 }
 
 extern "C" int p2p_coarse_matches(const float *corr4d, const uint8_t *delta, int hA, int wA, int hB, int wB, int ksize,

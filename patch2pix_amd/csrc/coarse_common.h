@@ -1,4 +1,4 @@
-// Shared by the coarse-stage sources: the kernels with their launchers (coarse.hip and matches.hip, which it includes; consensus.hip;
+// Shared by the coarse-stage sources: the kernels with their launchers (coarse.hip with matches.hip and score.hip, which it includes; consensus.hip;
 // consensus_generic.hip, included by coarse.hip) and the host API over them (coarse_api.hip).  Every source that defines one of
 // these functions includes this header, so a prototype that drifts from its definition does not compile.
 #pragma once
@@ -41,6 +41,16 @@ struct MatchArgs {
 void launch_matches(const MatchArgs &m, int batch, hipStream_t stream);                                  // one candidate, softmax score
 void launch_matches_topk(const MatchArgs &m, int batch, int topk, int do_softmax, hipStream_t stream);
 void launch_delta_unpack(const uint8_t *delta, size_t n, int k, long long *out, hipStream_t stream);
+
+// ---- score.hip --------------------------------------------------------------------------------------------------------------
+struct ScoreArgs {
+    const float *X;
+    float *cells;       // [pairs][nA + nB], the A cells first
+    float *pair;        // [pairs]
+    int nA, nB;
+    size_t sX;          // per-pair stride of the volume (cells)
+};
+void launch_score(const ScoreArgs &a, int batch, int normalize, hipStream_t stream);      // normalize: P2P_SCORE_*
 
 // ---- consensus.hip: the fused kernel of the released stack --------------------------------------------------------------
 void pack_nc_fused(const float *w1, const float *b1, const float *w2, DeviceBlob &out);      // lays out and fills the staging copy

@@ -232,6 +232,27 @@ class Patch2Pix(nn.Module):
         return ops.coarse_matches_topk_batch(corr4d[:, 0], self._packed_delta(delta4d, ksize), ksize, upsample, center,
                                              topk, do_softmax)
 
+    def cal_coarse_score(self, corr4d, normalize='softmax'):
+        """patch2pix.py:320-338: the NCNet pair score of corr4d [B,1,h1,w1,h2,w2] -- the mean over all cells of both images
+        (and over the batch) of the best normalised consensus value; normalize None, 'softmax' or 'l1'.  A 0-dim tensor on
+        the device: the fp32 mean of the B per-pair scores (every pair of a batch has the same cell count).  Any other
+        `normalize` raises ValueError."""
+        return ops.coarse_score_batch(corr4d[:, 0], normalize).mean()
+
+    def score_from_feats(self, feats1, feats2, ksize=2, normalize='softmax'):
+        """One score per pair from one coarse stage (non-reference): [B] fp32 on the device, cal_coarse_score of every pair
+        on its own, with no match extraction and no fine stage.  feats*: the pyramids (or any sequence whose last entry
+        is the [B,C,h,w] coarse feature map)."""
+        ops.score_norm(normalize)                  # a bad value raises before the coarse stage is paid for
+        corr4d, _ = self.forward_coarse_match(feats1[-1], feats2[-1], ksize=ksize)
+        return ops.coarse_score_batch(corr4d[:, 0], normalize)
+
+    def predict_score(self, im1, im2, ksize=2, normalize='softmax'):
+        """score_from_feats from the images: the call a re-ranking loop makes per shortlist batch."""
+        ops.score_norm(normalize)
+        feats1, feats2 = self._pyramids(im1, im2)
+        return self.score_from_feats(feats1, feats2, ksize, normalize)
+
     def shift_to_anchors(self, matches):
         """patch2pix.py:377-402: panc == 8 replaces each match by its 8 corner-shifted anchors."""
         if self.panc == 1:

@@ -580,6 +580,34 @@ def coarse_matches_topk_batch(corr, delta, ksize, upsample, center, topk, do_sof
     return matches, scores
 
 
+def score_norm(normalize):
+    """`normalize` of cal_coarse_score (None, 'softmax' or 'l1') -> P2P_SCORE_*; anything else raises ValueError (the
+    reference goes on to call the string and fails with a TypeError).  No GPU needed."""
+    if normalize is not None and not isinstance(normalize, str) or normalize not in _lib.SCORE_NORMS:
+        raise ValueError(f"normalize must be None, 'softmax' or 'l1', got {normalize!r}")
+    return _lib.SCORE_NORMS[normalize]
+
+
+def coarse_score_batch(corr, normalize="softmax", return_cells=False):
+    """cal_coarse_score (reference networks/patch2pix.py:320-338) per pair: corr [B,hA',wA',hB',wB'] fp32 GPU -> [B] fp32, the
+    mean over the nA + nB cells of both images of the best normalised consensus value (normalize: None, 'softmax', 'l1').
+    return_cells: also the cell scores [B, nA+nB], A cells first (the reference's torch.cat([scores_A, scores_B])).  A
+    pair's scores do not depend on the batch (include/p2p_hip.h)."""
+    norm = score_norm(normalize)
+    corr = _f32c(corr, "corr4d")
+    if corr.dim() != 5:
+        raise ValueError("coarse_score_batch expects corr4d of shape [B,hA,wA,hB,wB]")
+    nb, ha, wa, hb, wb = corr.shape
+    dev = corr.device
+    pair = torch.empty((nb,), dtype=torch.float32, device=dev)
+    cells = torch.empty((nb, ha * wa + hb * wb), dtype=torch.float32, device=dev)      # stream-ordered scratch when not returned
+    if nb:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.p2p_coarse_score_batch(corr.data_ptr(), nb, ha, wa, hb, wb, norm, cells.data_ptr(), pair.data_ptr(),
+                                                   None, 0, _stream()), "p2p_coarse_score_batch")
+    return (pair, cells) if return_cells else pair
+
+
 def filter_coarse_batch(matches, scores, ncn_thres=0.0, mutual=True):
     """filter_coarse (networks/utils.py:38-72, no ptmax) on the device for a batch: matches [B,n,4] int64, scores [B,n]
     fp32 -> (rows [B,n,4], scores [B,n], counts int32 [B]); the first counts[b] rows of item b are valid, in the

@@ -2,6 +2,7 @@
 
 Role of reference utils/eval/model_helper.py: `load_model(ckpt_path, method, lprint)`,
 `estimate_matches(net, im1, im2, ksize, ncn_thres, mutual, io_thres, eval_type, imsize)`,
+`estimate_score(net, im1, im2, ksize, normalize, imsize)` (non-reference: the pair score of `cal_coarse_score`),
 `refine_matches(im1_path, im2_path, net, coarse_matcher, io_thres, imsize, coarse_only)` and the two matcher
 factories `init_patch2pix_matcher(args)` / `init_ncn_matcher(args)`.  Signatures, defaults and return layouts are the
 reference's (what image-matching-toolbox binds to); the bodies are organised around the HIP library underneath.
@@ -145,6 +146,16 @@ def estimate_matches(net, im1, im2, ksize=2, ncn_thres=0.0, mutual=True, io_thre
     if confident.size:
         refined, confidence, proposals = refined[confident], confidence[confident], proposals[confident]
     return to_original * refined, confidence, to_original * proposals
+
+
+def estimate_score(net, im1, im2, ksize=2, normalize="softmax", imsize=None):
+    """The NCNet pair score of one image pair as a Python float (non-reference entry point; Patch2Pix.cal_coarse_score,
+    reference networks/patch2pix.py:320-338, on the pair's consensus volume): images loaded like estimate_matches loads
+    them (load_im_flexible), one coarse stage, no matches and no fine stage.  What a re-ranking loop calls per candidate."""
+    ops.score_norm(normalize)
+    t1, t2, _ = _load_pair(net, im1, im2, ksize, imsize)
+    with torch.no_grad():
+        return float(net.predict_score(t1, t2, ksize=ksize, normalize=normalize)[0])
 
 
 def estimate_matches_device(net, im1, im2, ksize=2, ncn_thres=0.0, mutual=True, io_thres=0.25, imsize=None, resize="host"):
