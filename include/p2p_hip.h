@@ -308,6 +308,53 @@ int p2p_match_tail_batch(const float *fine, const float *scores, const int64_t *
                          const double *scale, int batch, int stride, float io_thres, double *out_matches,
                          float *out_scores, double *out_coarse, int *out_counts, p2p_stream_t stream);
 
+/* Epipolar evaluation of match rows -- reference utils/eval/measure.py:18-71 (sampson_distance, symmetric_epipolar_distance),
+ * networks/utils.py:74-110 (sym_epi_dist, sampson_dist) and the np.histogram of check_inliers_distr (measure.py:115-141)
+ * (since version 109): per row (x1, y1, x2, y2) the distance to the epipolar geometry of the item's fundamental matrix, and per
+ * item the bin counts of those distances.  The inputs have the layout p2p_match_tail_batch leaves on the device.
+ *   matches [B,stride,4]  P2P_F64, P2P_F32 or P2P_I64 (matches_dtype), device
+ *   counts  [B] int32     device; valid rows per item.  -1 passes through: the item's hist row is zeros, its dist row untouched;
+ *                         0: the hist row is zeros.  A count above stride is read as stride
+ *   F       [B,9] fp64    device, row-major, x2^T F x1 = 0
+ *   edges   [nbins+1] fp64 device, ascending; together with hist, or both NULL (then nbins = 0)
+ *   dist    [B,stride]    P2P_F64 or P2P_F32 (dist_dtype); the first counts[b] entries of an item are written, the others left
+ *   hist    [B,nbins] int32, optional
+ * With the homogeneous third coordinate 1, l2 = F x1, l1 = F^T x2 and dd = x2 . l2:
+ *   P2P_EPI_SAMPSON   dd^2 / (eps + l1_0^2 + l1_1^2 + l2_0^2 + l2_1^2)              measure.py:39, networks/utils.py:109
+ *   P2P_EPI_SYM       dd^2 (1 / (eps + l1_0^2 + l1_1^2) + 1 / (eps + l2_0^2 + l2_1^2))     measure.py:70, networks/utils.py:92
+ *   P2P_EPI_SYM_SQRT  |dd| (1 / sqrt(eps + l1_0^2 + l1_1^2) + 1 / sqrt(eps + l2_0^2 + l2_1^2))   measure.py:67, networks/utils.py:90
+ *   P2P_EPI_VALUE     x1 itself: the first column holds distances computed earlier, which are stored and binned (the bin counts
+ *                     of check_inliers_distr for arrays that are distances already); F and eps are checked and not used
+ * eps = 0 is the numpy symmetric_epipolar_distance (which has no eps), 1e-8 the default of the other three functions.  A zero
+ * denominator gives what IEEE gives (0 / 0 = NaN, x / 0 = inf).
+ * ONE arithmetic, whatever the types: every input is widened to fp64 (exact for fp32; int64 beyond 2^53 rounds to nearest),
+ * everything is computed in fp64 in the order below -- fma is the fused operation, every other operation one IEEE operation,
+ * nothing is left to the compiler's contraction -- and the result is rounded once if dist is fp32 (the reference's d.float()):
+ *   l2_i = fma(F[3i], x1, fma(F[3i+1], y1, F[3i+2]))   i = 0, 1, 2        l1_j = fma(F[j], x2, fma(F[3+j], y2, F[6+j]))   j = 0, 1
+ *   dd = fma(x2, l2_0, fma(y2, l2_1, l2_2))     s1 = fma(l1_1, l1_1, l1_0 * l1_0)     s2 = fma(l2_1, l2_1, l2_0 * l2_0)
+ *   SAMPSON   (dd * dd) / ((eps + s1) + s2)
+ *   SYM       (dd * dd) * (1 / (eps + s1) + 1 / (eps + s2))
+ *   SYM_SQRT  fabs(dd) * (1 / sqrt(eps + s1) + 1 / sqrt(eps + s2))
+ * Histogram: np.histogram(dist, edges)[0] of the values AS STORED (after the rounding to fp32 if dist is fp32): bin i is
+ * [e_i, e_i+1), the last bin is closed on the right, values outside [e_0, e_nbins] and NaNs are not counted.  1 <= nbins <= 16.
+ * Counts are added with integer atomics in LDS only: they do not depend on any order.  Edges that do not ascend are the caller's
+ * error and cannot be seen on the host (the pointer is a device pointer): the counts are then meaningless, nothing else happens.
+ * A row's distance depends on the row and its item's F alone, an item's counts on its rows alone: both are bit-identical alone,
+ * in any batch, in any slot and for any stride >= counts[b].
+ * Null matches / counts / F / dist, batch outside 1..65535, stride < 1, an unknown dtype or kind, a negative or NaN eps, hist
+ * without edges or the reverse, nbins < 1 with a histogram or != 0 without -> P2P_EINVAL; nbins > 16 -> P2P_EUNSUPPORTED; all
+ * before the device is touched.  No workspace; one launch, one work-group per item (csrc/epipolar.hip), asynchronous on `stream`. */
+#define P2P_F32 0
+#define P2P_F64 1
+#define P2P_I64 2
+#define P2P_EPI_SAMPSON  0
+#define P2P_EPI_SYM      1
+#define P2P_EPI_SYM_SQRT 2
+#define P2P_EPI_VALUE    3
+int p2p_epipolar_batch(const void *matches, int matches_dtype, const int *counts, const double *F, int batch, int stride,
+                       int kind, double eps, const double *edges, int nbins, void *dist, int dist_dtype, int *hist,
+                       p2p_stream_t stream);
+
 /* ---- fine stage ------------------------------------------------------------------------------ */
 
 /* One image's feature pyramid levels feat_idx [0,1,2,3] (reference networks/resnet.py:138-157 with

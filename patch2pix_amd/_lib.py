@@ -133,6 +133,12 @@ p2p_filter_coarse_batch = _sig("p2p_filter_coarse_batch", ctypes.c_int,
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_stream])
 p2p_match_tail_batch = _sig("p2p_match_tail_batch", ctypes.c_int,
                             [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [ctypes.c_void_p] * 4 + [c_stream])
+p2p_epipolar_batch = _sig("p2p_epipolar_batch", ctypes.c_int,
+                          [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                           ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, c_stream])
+DTYPES = {"float32": 0, "float64": 1, "int64": 2}                   # P2P_F32 / _F64 / _I64
+EPI_KINDS = {"sampson": 0, "sym": 1, "sym_sqrt": 2, "value": 3}     # P2P_EPI_SAMPSON / _SYM / _SYM_SQRT / _VALUE
+EPI_MAX_BINS = 16
 p2p_regress = _sig("p2p_regress", ctypes.c_int,
                    [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Pyramid), ctypes.POINTER(Pyramid),
                     ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_void_p, ctypes.c_size_t, c_stream])
@@ -183,7 +189,7 @@ EXPORTS = ["p2p_version", "p2p_last_error", "p2p_ncn_create", "p2p_ncn_destroy",
            "p2p_maxpool_nhwc", "p2p_nhwc_to_nchw", "p2p_regressor_create_config", "p2p_regress_workspace_bytes_for",
            "p2p_coarse_matches_topk_batch", "p2p_ncn_create_config", "p2p_ncn_is_generic", "p2p_coarse_workspace_bytes_for",
            "p2p_neigh_consensus_workspace_bytes", "p2p_resize_workspace_bytes", "p2p_resize_bicubic_batch",
-           "p2p_coarse_score_workspace_bytes", "p2p_coarse_score_batch"]
+           "p2p_coarse_score_workspace_bytes", "p2p_coarse_score_batch", "p2p_epipolar_batch"]
 
 
 def check(status, what):

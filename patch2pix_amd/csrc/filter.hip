@@ -292,3 +292,5 @@ extern "C" int p2p_filter_coarse_batch(const int64_t *matches, const float *scor
     else hipLaunchKernelGGL(filter_coarse_kernel<false>, dim3(batch), dim3(FT), lds, (hipStream_t)stream, a);
     return check_launch("filter_coarse_kernel");
 }
+
+#include "epipolar.hip"      // p2p_epipolar_batch: distances and bin counts of the rows the tail leaves on the device

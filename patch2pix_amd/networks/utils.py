@@ -9,11 +9,14 @@ to "keep everything", and `ptmax` shuffles with the *global* numpy RNG and tiles
 Differences are mechanical only: the whole batch crosses PCIe once in each direction, and the
 row-wise unique runs on one packed 64-bit key per row (pixel coordinates are non-negative and
 < 2^15, so the key order is the lexicographic row order) instead of numpy's structured-view sort.
+
+`sym_epi_dist` / `sampson_dist` (reference networks/utils.py:74-110, `net.geo_dist_fn` and the label source of training):
+device tensors in, float32 device tensor out, one launch of p2p_epipolar_batch (csrc/epipolar.hip).
 """
 import numpy as np
 import torch
 
-from .. import staging
+from .. import ops, staging
 
 _ring = staging.PinnedRing(8)
 
@@ -67,3 +70,26 @@ def filter_coarse(coarse_matches, match_scores, ncn_thres=0.0, mutual=True, ptma
     # i.e. idle the GPU while the next launch is being prepared
     all_rows, all_scores = staging.upload([np.concatenate(out_rows), np.concatenate(out_scores)], device, _ring)
     return list(torch.split(all_rows, counts)), list(torch.split(all_scores, counts))
+
+
+def _epi_dist(matches, F, kind, eps):
+    if not torch.is_tensor(matches) or matches.dim() != 2 or matches.shape[1] != 4:
+        raise ValueError("matches must be an [N,4] tensor")
+    if matches.shape[0] == 0:
+        return torch.empty((0,), dtype=torch.float32, device=matches.device)
+    dist, _ = ops.epipolar_batch(matches[None], None, F, kind=kind, eps=eps, out_dtype=torch.float32)
+    return dist[0]
+
+
+def sym_epi_dist(matches, F, sqrt=True, eps=1e-8):
+    """Symmetric epipolar distance of matches [N,4] (float64, float32 or int64, on the GPU) under F [3,3] -> float32 [N] on the
+    GPU.  The reference's quirk is kept: it overwrites `sqrt` with False (networks/utils.py:88), so whatever the caller passes
+    the result is the SQUARED form with eps, dd^2 (1 / (eps + |l1|^2) + 1 / (eps + |l2|^2)).  Evaluated in fp64 and rounded
+    once (the reference evaluates in F's dtype and calls .float())."""
+    return _epi_dist(matches, F, "sym", eps)
+
+
+def sampson_dist(matches, F, eps=1e-8):
+    """Sampson distance dd^2 / (eps + |l1|^2 + |l2|^2) of matches [N,4] under F [3,3] -> float32 [N] on the GPU (reference
+    networks/utils.py:95-110); same types and arithmetic as sym_epi_dist."""
+    return _epi_dist(matches, F, "sampson", eps)

@@ -4,6 +4,7 @@ import ctypes
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib, staging
@@ -668,6 +669,88 @@ def match_tail_batch(fine, scores, coarse, counts, scale, io_thres):
     else:
         out_n.zero_()
     return out_m, out_s, out_c, out_n
+
+
+EPI_BINS_MEASURE = [0, 1e-2, 1, 5, 10, 25, 50, 100, 400, 2500, 1e5]      # default of check_inliers_distr (measure.py:116)
+EPI_BINS_EVAL = [0, 1e-2, 1, 5, 10, 25, 50, 100, 2500, 1e5]              # what eval_epoch_immatch.py:85 passes
+
+
+def epi_kind(kind):
+    """`kind` of epipolar_batch ('sampson', 'sym', 'sym_sqrt', or 'value' for distances that are only binned) -> P2P_EPI_*; anything else raises ValueError.  No GPU needed."""
+    if not isinstance(kind, str) or kind not in _lib.EPI_KINDS:
+        raise ValueError(f"kind must be one of {sorted(_lib.EPI_KINDS)}, got {kind!r}")
+    return _lib.EPI_KINDS[kind]
+
+
+def epi_edges(bins):
+    """The nbins + 1 bin edges of epipolar_batch as a float64 array, checked where they still are on the host: one dimension,
+    2 to 17 values, no NaN, ascending (np.histogram's own condition).  ValueError otherwise; more than 16 bins
+    NotImplementedError.  No GPU needed."""
+    edges = np.asarray(bins, dtype=np.float64)
+    if edges.ndim != 1 or edges.size < 2:
+        raise ValueError(f"bins must be a one-dimensional sequence of at least two edges, got shape {edges.shape}")
+    if np.isnan(edges).any() or bool((np.diff(edges) < 0).any()):
+        raise ValueError("bins must increase monotonically and hold no NaN")
+    if edges.size - 1 > _lib.EPI_MAX_BINS:
+        raise NotImplementedError(f"{edges.size - 1} bins: at most {_lib.EPI_MAX_BINS} are implemented")
+    return edges
+
+
+def epipolar_batch(matches, counts, F, kind="sampson", eps=1e-8, bins=None, out_dtype=None):
+    """Distances of match rows to the epipolar geometry of their pair's fundamental matrix, and their bin counts, on the device
+    (reference utils/eval/measure.py:18-71,115-141 and networks/utils.py:74-110; include/p2p_hip.h, p2p_epipolar_batch):
+    matches [B,n,4] float64, float32 or int64 on the GPU (x1, y1, x2, y2), counts int32 [B] on the GPU (valid rows per item; -1
+    passes through) or None (all n rows), F [B,3,3] or [3,3] (x2^T F x1 = 0; a single matrix serves B = 1), kind 'sampson' |
+    'sym' | 'sym_sqrt', eps 0 for the numpy symmetric distance, bins a host sequence of ascending edges or None.
+    -> (dist [B,n] of out_dtype (default float64), rows beyond counts[b] zero; hist int32 [B,nbins] or None)."""
+    code = epi_kind(kind)
+    eps = float(eps)
+    if not eps >= 0.0:
+        raise ValueError(f"eps must be >= 0, got {eps!r}")
+    edges = epi_edges(bins) if bins is not None else None
+    if not torch.is_tensor(matches) or matches.dim() != 3 or matches.shape[-1] != 4:
+        raise ValueError("matches must be a [B,n,4] tensor")
+    nb, n, _ = matches.shape
+    F = torch.as_tensor(F)
+    if tuple(F.shape) == (3, 3) and nb == 1:
+        F = F[None]
+    if tuple(F.shape) != (nb, 3, 3):
+        raise ValueError(f"F must have shape [{nb},3,3] (or [3,3] for one item), got {tuple(F.shape)}")
+    out_dtype = torch.float64 if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"out_dtype must be torch.float64 or torch.float32, got {out_dtype}")
+    if counts is not None and (not torch.is_tensor(counts) or counts.numel() != nb):
+        raise ValueError(f"counts must be an int32 tensor of {nb} values or None")
+    name = str(matches.dtype).replace("torch.", "")
+    if name not in _lib.DTYPES or not matches.is_cuda:
+        raise TypeError(f"matches must be a float64, float32 or int64 tensor on the GPU (got {matches.dtype}, {matches.device})")
+    if counts is not None and (counts.dtype != torch.int32 or counts.device != matches.device):
+        raise TypeError("counts must be an int32 tensor on the device of matches")
+    dev = matches.device
+    matches = matches.contiguous()
+    dist = torch.zeros((nb, n), dtype=out_dtype, device=dev)
+    hist = torch.zeros((nb, len(edges) - 1), dtype=torch.int32, device=dev) if edges is not None else None
+    if nb == 0 or n == 0:
+        return dist, hist
+    if nb > 65535:
+        raise ValueError(f"epipolar_batch: {nb} items (at most 65535 per call)")
+    with torch.cuda.device(dev):
+        if F.is_cuda:
+            Fd = F.to(dev, torch.float64).contiguous()
+            dedges = small_to_device(edges, torch.float64, dev) if edges is not None else None
+        else:          # F and the edges in ONE copy through the staging ring
+            parts = [F.to(torch.float64).contiguous()] + ([torch.from_numpy(edges)] if edges is not None else [])
+            up = staging.upload(parts, dev, _small_ring)
+            Fd, dedges = up[0], (up[1] if edges is not None else None)
+        if counts is None:
+            counts = torch.full((nb,), n, dtype=torch.int32, device=dev)
+        counts = counts.contiguous()
+        _lib.check(_lib.p2p_epipolar_batch(matches.data_ptr(), _lib.DTYPES[name], counts.data_ptr(), Fd.data_ptr(), nb, n,
+                                           code, eps, dedges.data_ptr() if edges is not None else None,
+                                           len(edges) - 1 if edges is not None else 0, dist.data_ptr(),
+                                           _lib.DTYPES[str(out_dtype).replace("torch.", "")],
+                                           hist.data_ptr() if hist is not None else None, _stream()), "p2p_epipolar_batch")
+    return dist, hist
 
 
 def regress_batch_dev(reg1, reg2, pyrs1, pyrs2, proposals, counts, want_raw=False, out=None):

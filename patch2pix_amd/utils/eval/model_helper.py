@@ -24,6 +24,7 @@ from ..datasets.preprocess import (decode_pixels, load_im_flexible, load_im_pixe
                                    resize_pixels_device, upload_pixels)
 from ...networks.patch2pix import Patch2Pix
 from ... import ops
+from .measure import EpipolarReport
 
 _SILENT = lambda *a, **k: None
 
@@ -158,23 +159,71 @@ def estimate_score(net, im1, im2, ksize=2, normalize="softmax", imsize=None):
         return float(net.predict_score(t1, t2, ksize=ksize, normalize=normalize)[0])
 
 
-def estimate_matches_device(net, im1, im2, ksize=2, ncn_thres=0.0, mutual=True, io_thres=0.25, imsize=None, resize="host"):
+def check_fundamental(F):
+    """A fundamental matrix argument as a float64 [3,3] numpy array; ValueError for any other shape.  No GPU needed."""
+    F = F.detach().cpu().numpy() if torch.is_tensor(F) else np.asarray(F)
+    if F.shape != (3, 3):
+        raise ValueError(f"a fundamental matrix must have shape [3,3], got {F.shape}")
+    return F.astype(np.float64)
+
+
+def epipolar_device(m, c, n, fundamentals, bins):
+    """The Sampson distances and bin counts of the tail's device outputs (m, c [B,stride,4] float64, n int32 [B]) under the
+    pairs' fundamental matrices [B,3,3] (host): one p2p_epipolar_batch call per list -> (fdist, fhist, cdist, chist) on the
+    device.  Nothing here waits for the GPU."""
+    Fd = ops.small_to_device(np.asarray(fundamentals, dtype=np.float64).reshape(-1, 3, 3), torch.float64, m.device)
+    fdist, fhist = ops.epipolar_batch(m, n, Fd, kind="sampson", bins=bins)
+    cdist, chist = ops.epipolar_batch(c, n, Fd, kind="sampson", bins=bins)
+    return fdist, fhist, cdist, chist
+
+
+def epipolar_report(matches, coarse, F, bins):
+    """The EpipolarReport of rows that are on the host already (the pairs the device filter hands back to the host path):
+    the same kernel on an upload of them."""
+    k = len(matches)
+    nb = len(bins) - 1
+    if k == 0:
+        return EpipolarReport(np.empty(0), np.empty(0), np.zeros(nb, np.int64), np.zeros(nb, np.int64), list(bins), 0)
+    device = torch.device("cuda", torch.cuda.current_device())
+    both = ops.small_to_device(np.stack([matches, coarse]).astype(np.float64), torch.float64, device)
+    dist, hist = ops.epipolar_batch(both, None, np.stack([F, F]), kind="sampson", bins=bins)
+    dist, hist = _host(dist), _host(hist).astype(np.int64)
+    return EpipolarReport(dist[0], dist[1], hist[0], hist[1], list(bins), k)
+
+
+def estimate_matches_device(net, im1, im2, ksize=2, ncn_thres=0.0, mutual=True, io_thres=0.25, imsize=None, resize="host",
+                            fundamental=None, bins=None):
     """estimate_matches(eval_type='fine') with NOTHING between the image tensors and the result on the host
     (non-reference entry point): coarse stage, filter_coarse, both regressors and the io_thres / scaling tail of
     model_helper.py:92-109 all run on the device; one device-to-host copy at the end.  Same return triple.
     resize="device": the bicubic resize runs on the device as well (csrc/preprocess.hip, equal to Pillow's bit for bit); the
-    host only decodes."""
+    host only decodes.
+    fundamental: a [3,3] matrix F with x2^T F x1 = 0 in ORIGINAL-image pixels adds a fourth value, an EpipolarReport
+    (utils/eval/measure.py): the Sampson distances of the kept fine and coarse rows and their counts over `bins` (default: the
+    list of the reference's eval_epoch_immatch.py:85), computed on the tail's device outputs before the copy -- what
+    eval_epoch_immatch.py:62-63,85-87 computes on the host."""
     if resize not in ("host", "device"):
         raise ValueError(f"resize must be 'host' or 'device', got {resize!r}")
+    if fundamental is not None:
+        fundamental = check_fundamental(fundamental)
+        bins = list(ops.EPI_BINS_EVAL if bins is None else bins)
+        ops.epi_edges(bins)
     t1, t2, to_original = (_load_pair_device if resize == "device" else _load_pair)(net, im1, im2, ksize, imsize)
     with torch.no_grad():
         fine, scores, coarse, counts = net.predict_fine_device(net.extract.pyramid(t1), net.extract.pyramid(t2), ksize=ksize,
                                                                ncn_thres=ncn_thres, mutual=mutual)
         m, s, c, n = ops.match_tail_batch(fine, scores, coarse, counts, to_original, io_thres)
+        epi = epipolar_device(m, c, n, fundamental[None], bins) if fundamental is not None else None
     k = int(n[0])
     if k < 0:          # a coordinate outside the device filter's packed key: the reference path
-        return estimate_matches(net, im1, im2, ksize, ncn_thres, mutual, io_thres, "fine", imsize)
-    return _host(m[0, :k]), _host(s[0, :k]), _host(c[0, :k])
+        out = estimate_matches(net, im1, im2, ksize, ncn_thres, mutual, io_thres, "fine", imsize)
+        return out if fundamental is None else out + (epipolar_report(out[0], out[2], fundamental, bins),)
+    out = _host(m[0, :k]), _host(s[0, :k]), _host(c[0, :k])
+    if fundamental is None:
+        return out
+    fdist, fhist, cdist, chist = epi
+    return out + (EpipolarReport(_host(fdist[0, :k]), _host(cdist[0, :k]), _host(fhist[0]).astype(np.int64),
+                                 _host(chist[0]).astype(np.int64), bins, k),)
 
 
 def refine_matches(im1_path, im2_path, net, coarse_matcher, io_thres=0.0, imsize=None, coarse_only=False):

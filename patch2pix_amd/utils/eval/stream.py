@@ -99,18 +99,27 @@ def _collect(rec, io_thres):
     return out
 
 
-def _issue_device(net, f1, f2, group, ksize, ncn_thres, mutual, io_thres):
+def _issue_device(net, f1, f2, group, ksize, ncn_thres, mutual, io_thres, epi=None):
     """Coarse stage, device-side filter_coarse, both regressors and the io_thres / scaling tail of the batch enqueued,
-    the padded results on their way to pinned memory.  Nothing here waits for the GPU."""
+    the padded results on their way to pinned memory.  Nothing here waits for the GPU.  epi = (fundamentals, bins): the
+    batch's epipolar distances and bin counts (two more launches on the tail's outputs) travel in the same slot."""
     from ... import ops
     fine, scores, coarse, counts = net.predict_fine_device(f1, f2, ksize=ksize, ncn_thres=ncn_thres, mutual=mutual)
     scale = np.concatenate([g[3] for g in group]).astype(np.float64)
     outs = ops.match_tail_batch(fine, scores, coarse, counts, scale, io_thres)
-    return dict(staged=staging.readback(outs, _dev_ring), jobs=[g[4] for g in group])
+    if epi is not None:
+        from .model_helper import epipolar_device
+        outs = tuple(outs) + epipolar_device(outs[0], outs[2], outs[3], [epi[0][g[0]] for g in group], epi[1])
+    return dict(staged=staging.readback(outs, _dev_ring), jobs=[g[4] for g in group], epi=epi)
 
 
 def _collect_device(net, rec, ncn_thres, mutual, io_thres):
-    m, s, c, n = _staged(rec)
+    m, s, c, n, *dists = _staged(rec)
+    epi = rec.get("epi")
+    if epi is not None:
+        from .measure import EpipolarReport
+        from .model_helper import epipolar_report
+        fdist, fhist, cdist, chist = dists
     out = []
     for b, job in enumerate(rec["jobs"]):
         k = int(n[b])
@@ -119,10 +128,17 @@ def _collect_device(net, rec, ncn_thres, mutual, io_thres):
             for f in (job[1], job[2]):      # file objects were read by the loader thread: rewind them for the second decode
                 if hasattr(f, "seek"):
                     f.seek(0)
-            out.append(estimate_matches(net, job[1], job[2], ksize=job[3], ncn_thres=ncn_thres, mutual=mutual, io_thres=io_thres,
-                                        eval_type="fine", imsize=job[5]))
+            item = estimate_matches(net, job[1], job[2], ksize=job[3], ncn_thres=ncn_thres, mutual=mutual, io_thres=io_thres,
+                                    eval_type="fine", imsize=job[5])
+            if epi is not None:
+                item += (epipolar_report(item[0], item[2], epi[0][job[0]], epi[1]),)
+            out.append(item)
         else:
-            out.append((m[b, :k].copy(), s[b, :k].copy(), c[b, :k].copy()))
+            item = (m[b, :k].copy(), s[b, :k].copy(), c[b, :k].copy())
+            if epi is not None:
+                item += (EpipolarReport(fdist[b, :k].copy(), cdist[b, :k].copy(), fhist[b].astype(np.int64),
+                                        chist[b].astype(np.int64), list(epi[1]), k),)
+            out.append(item)
     return out
 
 
@@ -150,20 +166,33 @@ def _bounded_map(pool, fn, jobs, ahead):
 
 
 def estimate_matches_stream(net, pairs, ksize=2, ncn_thres=0.0, mutual=True, io_thres=0.25, imsize=None,
-                            batch=8, workers=4, lookahead=None, device_filter=True, resize="host"):
+                            batch=8, workers=4, lookahead=None, device_filter=True, resize="host", fundamentals=None):
     """Generator over `pairs` (iterable of (im1, im2) paths / file objects): yields
     (matches float64 [M,4], scores float32 [M], coarse_matches float64 [M,4]) per pair, in order.
     workers: loader threads (a 480x640 JPEG pair decodes in 2 ms: a few threads feed the GPU); lookahead: pairs decoded
     ahead of the batch being matched (default 3 batches); device_filter=False keeps filter_coarse on the host (the
     reference's numpy semantics literally; same results, tests/test_gpu_parity.py); resize="device": the loader threads
     only decode, the bicubic resize (Pillow's, bit for bit: csrc/preprocess.hip) and the normalisation of a whole batch are
-    one call on the device -- same results (tests/test_gpu_resize.py)."""
+    one call on the device -- same results (tests/test_gpu_resize.py).
+    fundamentals: a sequence of one [3,3] fundamental matrix per pair (x2^T F x1 = 0 in original-image pixels; `pairs` must
+    then be a sequence as well) adds a fourth value to every item, the EpipolarReport estimate_matches_device(...,
+    fundamental=F) returns, computed per batch on the device path (which it needs)."""
     if resize not in ("host", "device"):
         raise ValueError(f"resize must be 'host' or 'device', got {resize!r}")
+    epi = None
+    if fundamentals is not None:
+        from ... import ops
+        from .model_helper import check_fundamental
+        pairs = list(pairs)
+        if len(fundamentals) != len(pairs):
+            raise ValueError(f"fundamentals holds {len(fundamentals)} matrices for {len(pairs)} pairs")
+        epi = ([check_fundamental(F) for F in fundamentals], list(ops.EPI_BINS_EVAL))
     if resize == "device" and torch.device(net.device).type != "cuda":
         raise ValueError("resize='device' needs the network on a GPU")
     on_device = (device_filter and torch.device(net.device).type == "cuda" and getattr(net, "panc", 1) == 1
                  and hasattr(net, "predict_fine_device"))
+    if epi is not None and not on_device:
+        raise ValueError("fundamentals needs the device path (device_filter=True, a network on a GPU with panc 1)")
     jobs = ((i, a, b, ksize, net.upsample, imsize, resize) for i, (a, b) in enumerate(pairs))
     pending = deque()          # (ticket, metas) whose fine stage has not been issued yet
     issued = deque()           # batches whose fine stage is enqueued and whose results are being copied to the host
@@ -186,7 +215,7 @@ def estimate_matches_stream(net, pairs, ksize=2, ncn_thres=0.0, mutual=True, io_
                 im2 = _upload([g[2] for g in group], net.device)
             f1, f2 = pair_pyramids(net.extract, im1, im2, both)
             if on_device:
-                issued.append(_issue_device(net, f1, f2, group, ksize, ncn_thres, mutual, io_thres))
+                issued.append(_issue_device(net, f1, f2, group, ksize, ncn_thres, mutual, io_thres, epi))
             else:
                 pending.append((net.coarse_async(f1, f2, ksize=ksize), [g[3] for g in group]))
             group.clear()
