@@ -98,20 +98,42 @@ def _bn(x, p, prefix, shape):
     return (x - g("running_mean")) / torch.sqrt(g("running_var") + 1e-5) * g("weight") + g("bias")
 
 
-def regressor_forward(f1, f2, p, case):
-    """FeatRegressNet.forward (modules.py:101-112) in eval mode, in the dtype of its arguments -> raw [N,5]."""
+WINO_BT = ((1, 0, -1, 0), (0, 1, 1, 0), (0, -1, 1, 0), (0, 1, 0, -1))      # B^T of Winograd F(2x2, 3x3)
+
+
+def wino_input_transform(h):
+    """B^T d B over the sixteen 4 x 4 windows d (stride 2) of the zero-ringed 8 x 8 map h [N,C,8,8], in h's dtype ->
+    [N, 16 windows (ty * 4 + tx), 16 positions (i * 4 + j), C]."""
+    bt = torch.tensor(WINO_BT, dtype=h.dtype)
+    d = F.pad(h, (1, 1, 1, 1)).unfold(2, 4, 2).unfold(3, 4, 2)          # [N,C,ty,tx,a,b]
+    u = torch.einsum("ia,nctxab,jb->ntxijc", bt, d, bt)
+    return u.reshape(h.shape[0], 16, 16, h.shape[1])
+
+
+def regressor_forward(f1, f2, p, case, stages=False):
+    """FeatRegressNet.forward (modules.py:101-112) in eval mode, in the dtype of its arguments -> raw [N,5].
+    stages (the two-convolution 'pre' configurations with an 8 x 8 map, case "R"): -> (raw, H, U, V) with H = BN1(conv1(x))
+    [N,C,8,8] (no ReLU: the network has none there), U = wino_input_transform(H), V = relu(max(BN2(conv2(H)))) [N,C] --
+    the values the tuned kernels hand from one launch to the next (tests/stage_reference.py)."""
     c = CASES[case]
+    kept = []
 
     def conv(u):
         for i, st in enumerate(c["conv_strs"]):
             u = _bn(F.conv2d(u, p[f"conv.{2 * i}.weight"], None, stride=st, padding=1), p, f"conv.{2 * i + 1}", (1, -1, 1, 1))
+            kept.append(u)
         return F.relu(u).amax(dim=(2, 3))          # one ReLU after the last BatchNorm, MaxPool over the whole map
 
     v = torch.cat([conv(f1), conv(f2)], dim=1) if c["feat_comb"] == "post" else conv(torch.cat([f1, f2], dim=1))
+    pooled = v
     for i in range(len(c["fc_dims"])):
         v = F.relu(_bn(F.linear(v, p[f"fc.{3 * i}.weight"], p[f"fc.{3 * i}.bias"]), p, f"fc.{3 * i + 1}", (1, -1)))
     n = 3 * len(c["fc_dims"])
-    return F.linear(v, p[f"fc.{n}.weight"], p[f"fc.{n}.bias"])
+    raw = F.linear(v, p[f"fc.{n}.weight"], p[f"fc.{n}.bias"])
+    if not stages:
+        return raw
+    assert c["feat_comb"] == "pre" and len(kept) == 2 and kept[0].shape[2:] == (8, 8), "stages: a two-convolution 'pre' net on an 8 x 8 map"
+    return raw, kept[0], wino_input_transform(kept[0]), pooled
 
 
 def fine_level(pyr1, pyr2, matches, p, case):
