@@ -1,7 +1,10 @@
 // Neighbourhood consensus (reference networks/ncn/model.py:145-155, conv4d.py:12-74; 1 -> 16 -> 1 channels, kernel 3^4, both
 // symmetric branches) as ONE kernel on the fp16 matrix cores: the 16-channel hidden volume never leaves the compute unit.
 //
-// Work-group = one branch x one output tile [TA a][TB b][TC c][TD d] of the volume Y[a][b][c][d].  It walks the hidden
+// Work-group = one output tile [TA a][TB b][TC c][TD d] of the volume Y[a][b][c][d], BOTH branches: eight waves, waves 0-3 the
+// direct branch, waves 4-7 the transposed one (the same volume X with A/B-swapped taps, pack_nc_fused).  The staged input
+// planes (S1) are shared by the two halves and staged once by all eight waves; weights (registers), hidden planes, output
+// accumulators and flush target are per half.  The work-group walks the hidden
 // "strips" (a', b') that feed the tile in SERPENTINE order (a' ascending; b' ascending in even rows of the GLOBAL index a',
 // descending in odd ones), so that every step brings exactly ONE new triple of input planes.  Per strip:
 //   S1  the 9 planes (da, db) of the input X (first MutualMatching applied) around the strip live in LDS as two fp16 planes
@@ -42,7 +45,7 @@ namespace p2p {
 typedef _Float16 nh8 __attribute__((ext_vector_type(8)));
 typedef float nf4 __attribute__((ext_vector_type(4)));
 
-constexpr int NCF_THREADS = 256, NCF_WAVES = 4;
+constexpr int NCF_THREADS = 512, NCF_WAVES = 8, NCF_HWAVES = 4;      // waves per work-group, per branch (half)
 constexpr int NCF_W1_BYTES = 7 * 2 * 64 * 16;      // layer-1 B fragments [slab][plane][lane][8 fp16]
 constexpr int NCF_W2_BYTES = 5 * 2 * 64 * 16;      // layer-2 B fragments [K step][plane][lane][8 fp16]
 constexpr int NCF_C_FLOATS = 64;                   // s1[16], b1[16], hscale, yunscale, padding
@@ -104,17 +107,25 @@ __device__ __forceinline__ float npk_hi(unsigned h) { return (float)__builtin_bi
 #define NT_DECL
 #define NT(i)
 #endif
-constexpr int NCF_KRING = 5;     // items per wave and triple of planes: ceil(3 planes x 6 row pairs / 4 waves)
+constexpr int NCF_KRING = 3;     // items per wave and triple of planes: ceil(3 planes x 6 row pairs / 8 waves)
 
-// FIXED: the tile (tb, tc, td, P) = (5, 8, 40, 44) of every 480x640 / 960x1280 pair (pooled rows of 40 or 80 cells) as
+// Bytes of one fp16 plane of the staged input: nine ring slots of (tc + 4) rows, 16-byte aligned for what lies behind it.
+// The window of a plane's last position pair reads 4 bytes past the ninth slot (into the next plane / the hidden planes:
+// inside the allocation); that pair is the last two columns of the pitch, which are never cells (P >= td + 4), so what is
+// read there only reaches accumulators that are dropped.
+__host__ __device__ __forceinline__ int nc_xplane(int tc, int P) { return (9 * (tc + 4) * P * 2 + 15) & ~15; }
+
+// FTB > 0: the tile (tb, tc, td, P) = (FTB, 8, 40, 44) of every 480x640 / 960x1280 pair (pooled rows of 40 or 80 cells) as
 // compile-time constants -- strides, divisions and the LDS carve-up fold away (the generic body spends more instructions on
-// scalar bookkeeping than on the matrix pipe: ~2100 per strip and wave for 72 MFMAs); any other shape runs the same body
-// with the runtime values.
-template <bool FIXED>
-__global__ __launch_bounds__(NCF_THREADS, 2) void nc_fused_kernel(NcFusedArgs a) {
+// scalar bookkeeping than on the matrix pipe: ~2100 per strip and wave for 72 MFMAs); FTB = 0: any other shape runs the
+// same body with the runtime values.  One work-group per compute unit (FTB = 10: all 160 KB of its LDS), two waves per SIMD.
+template <int FTB>
+__global__ __launch_bounds__(NCF_THREADS, 1) void nc_fused_kernel(NcFusedArgs a) {
     P2P_DYN_SHARED(unsigned char, sm);
+    constexpr bool FIXED = FTB > 0;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int br = blockIdx.y;
+    // the half of the work-group (wave-uniform): branch br, and this wave's place hw among the four waves of its branch
+    const int br = wave >> 2, hw = wave & 3;
     const float *X = a.X + (size_t)blockIdx.z * a.stride;
     float *Y = ((br && a.Y2) ? a.Y2 : a.Y) + (size_t)blockIdx.z * a.stride;
     const bool plain = a.Y2 != nullptr;
@@ -123,18 +134,20 @@ __global__ __launch_bounds__(NCF_THREADS, 2) void nc_fused_kernel(NcFusedArgs a)
     const int c0 = (g % a.nc) * a.tc; g /= a.nc;
     const int b0 = (g % a.nb) * a.tb; g /= a.nb;
     const int a0 = g * a.ta;
-    const int TA = a.ta, TB = FIXED ? 5 : a.tb, TC = FIXED ? 8 : a.tc, TD = FIXED ? 40 : a.td, P = FIXED ? 44 : a.P;
+    const int TA = a.ta, TB = FIXED ? FTB : a.tb, TC = FIXED ? 8 : a.tc, TD = FIXED ? 40 : a.td, P = FIXED ? 44 : a.P;
     const int XROWS = TC + 4, HROWS = TC + 2;
     const int HNU = FIXED ? nc_hidden_used(8, 44) : nc_hidden_used(TC, P), HN = FIXED ? nc_hidden_slots(8, 44) : nc_hidden_slots(TC, P);
-    const int XPLANE = (9 * XROWS * P * 2 + 8 + 15) & ~15;   // bytes of one fp16 plane of the staged input (+ the window overrun of its
-                                                             // last position; the hidden planes behind it need 16-byte alignment)
+    const int XPLANE = FIXED ? nc_xplane(8, 44) : nc_xplane(TC, P);      // bytes of one fp16 plane of the staged input
     const int HKH = HN * 16, HPLANE = 2 * HKH;               // hidden: [plane][channel half][position][8 x fp16]
     // accumulators: [3 slots][TB][TC * P (+ pad)] floats; the pad (stride = 4 mod 8 floats... = 16 B mod 32 B, and never a
     // multiple of 64 floats) spreads the nine planes a layer-2 tile adds into over the LDS banks
     const int YROW = nc_yrow(TC, P), YSLOT = TB * YROW;
+    // LDS: the staged input (shared) | hidden planes of branch 0, of branch 1 | accumulators of branch 0, of branch 1.  A
+    // branch's hidden region is 4 channel halves long, so both branches keep the bank-slot property above; the accumulator
+    // regions are whole rows of the pitch YROW.
     unsigned char *Xs = sm;
-    unsigned char *Hs = sm + 2 * XPLANE;
-    float *Ya = (float *)(Hs + 2 * HPLANE);
+    unsigned char *Hs = sm + 2 * XPLANE + br * 2 * HPLANE;
+    float *Ya = (float *)(sm + 2 * XPLANE + 4 * HPLANE) + br * 3 * YSLOT;
     const size_t nB = (size_t)a.d2 * a.d3;
 
     // weights of this branch -> registers (layer 1: the A operands of its MFMAs)
@@ -179,11 +192,11 @@ __global__ __launch_bounds__(NCF_THREADS, 2) void nc_fused_kernel(NcFusedArgs a)
         for (int c = 0; c < 16; ++c) { e1s[c] = cf[c] * up * hscale; e1b[c] = cf[16 + c] * hscale; }
     }
 
-    for (int i = tid; i < 3 * YSLOT; i += NCF_THREADS) Ya[i] = 0.f;
+    for (int i = tid; i < 2 * 3 * YSLOT; i += NCF_THREADS) ((float *)(sm + 2 * XPLANE + 4 * HPLANE))[i] = 0.f;
     // The hidden planes start as zeros: the pad slots around the positions and every position outside the volume stay zero
     // for the whole kernel (which positions those are depends on (c, d) only, not on the strip) -- their lanes store
     // to the spare slot HNU instead (HN - HNU = 14 spare slots per channel half).
-    for (int i = tid; i < 2 * HPLANE / 16; i += NCF_THREADS) *(nf4 *)(Hs + i * 16) = (nf4){0.f, 0.f, 0.f, 0.f};
+    for (int i = tid; i < 4 * HPLANE / 16; i += NCF_THREADS) *(nf4 *)(sm + 2 * XPLANE + i * 16) = (nf4){0.f, 0.f, 0.f, 0.f};
 
     const int a_hi = min(a0 + TA, a.d0);                     // outputs of the tile: [a0, a_hi)
     const int ap_first = max(a0 - 1, 0), ap_last = min(a0 + TA, a.d0 - 1);
@@ -212,16 +225,16 @@ __global__ __launch_bounds__(NCF_THREADS, 2) void nc_fused_kernel(NcFusedArgs a)
         };
         if (FIXED) {
 #pragma unroll 2
-            for (int i = 0; i < 10; ++i) row(wave + NCF_WAVES * i);
+            for (int i = 0; i < 2 * FTB; ++i) row(hw + NCF_HWAVES * i);
         } else {
-            for (int r = wave; r < TB * TC; r += NCF_WAVES) row(r);
+            for (int r = hw; r < TB * TC; r += NCF_HWAVES) row(r);
         }
     };
 
     // ---- S1: this lane's pair of columns of a staged row (strip-independent)
     const int nbp = bp_last - bp_first + 1, nstrips = (ap_last - ap_first + 1) * nbp;
     const int sB = (int)nB, sA = a.d1 * sB;                  // 32-bit element offsets (a volume has < 2^31 cells)
-    // Lanes and items beyond the layout (column pairs >= P / 2, rows >= XROWS, items 18 and 19) are made exact DUPLICATES of the
+    // Lanes and items beyond the layout (column pairs >= P / 2, rows >= XROWS, items 18 to 23) are made exact DUPLICATES of the
     // last valid column pair / row: same source, same destination, same value -- so the staging needs no validity branches.
     const int cp = min(lane & 31, P / 2 - 1), rh = lane >> 5;
     const int dcol = dt0 - 2 + 2 * cp;
@@ -252,8 +265,8 @@ __global__ __launch_bounds__(NCF_THREADS, 2) void nc_fused_kernel(NcFusedArgs a)
     // byte offset of the plane's slot.
     int isrc[NCF_KRING], idst[NCF_KRING];
     bool iin[NCF_KRING];
-    // (three plane descriptors per strip; item k of wave w belongs to plane min((w + 4 k) / 6, 2): 0, w >= 2, 1, 2, 2)
-    const bool k1_second = wave >= 2;
+    // (three plane descriptors per strip; item k of wave w belongs to plane min((w + 8 k) / 6, 2): w >= 6, 1 + (w >= 4), 2)
+    const bool k0_second = wave >= 6, k1_third = wave >= 4;
     auto rot3 = [](int m, int i) { return m + i >= 3 ? m + i - 3 : m + i; };      // (m + i) mod 3 for m in 0..2, i in 0..2
     // ma, mb = ring slot (pa mod 3, pb mod 3) of the triple's first plane; the others follow cyclically
     auto triple = [&](int pa, int pb, bool along_a, int ma, int mb) {
@@ -267,13 +280,11 @@ __global__ __launch_bounds__(NCF_THREADS, 2) void nc_fused_kernel(NcFusedArgs a)
             in3[i] = ia >= 0 && ia < a.d0 && ib >= 0 && ib < a.d1;
             dst3[i] = (sa * 3 + sb) * XROWS * P * 2;
         }
-        isrc[0] = src3[0]; iin[0] = in3[0]; idst[0] = dst3[0];
-        isrc[1] = k1_second ? src3[1] : src3[0]; iin[1] = k1_second ? in3[1] : in3[0]; idst[1] = k1_second ? dst3[1] : dst3[0];
-        isrc[2] = src3[1]; iin[2] = in3[1]; idst[2] = dst3[1];
-        isrc[3] = src3[2]; iin[3] = in3[2]; idst[3] = dst3[2];
-        isrc[4] = src3[2]; iin[4] = in3[2]; idst[4] = dst3[2];
+        isrc[0] = k0_second ? src3[1] : src3[0]; iin[0] = k0_second ? in3[1] : in3[0]; idst[0] = k0_second ? dst3[1] : dst3[0];
+        isrc[1] = k1_third ? src3[2] : src3[1]; iin[1] = k1_third ? in3[2] : in3[1]; idst[1] = k1_third ? dst3[2] : dst3[1];
+        isrc[2] = src3[2]; iin[2] = in3[2]; idst[2] = dst3[2];
     };
-    static_assert(NCF_KRING == 5 && NCF_WAVES == 4, "the item -> plane table above");
+    static_assert(NCF_KRING == 3 && NCF_WAVES == 8, "the item -> plane table above");
     // the current triple: loads (unconditional, from clamped addresses; the zero padding is selected when the value is used) ...
     auto ring_load = [&]() {
 #pragma unroll
@@ -304,7 +315,7 @@ __global__ __launch_bounds__(NCF_THREADS, 2) void nc_fused_kernel(NcFusedArgs a)
     unsigned s2ok = 0;                                        // bit 2 u + s: position q0(u) + 2 l31 + s is a cell of the volume
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-        const int t = wave + NCF_WAVES * u, q0 = t * 64;
+        const int t = hw + NCF_HWAVES * u, q0 = t * 64;
         s2qh[u] = min(q0 + 2 * l31, HROWS * P - 2);           // columns past the strip repeat its last pair (never stored)
 #pragma unroll
         for (int sp = 0; sp < 2; ++sp) {
@@ -421,7 +432,7 @@ __global__ __launch_bounds__(NCF_THREADS, 2) void nc_fused_kernel(NcFusedArgs a)
             // q0 + 2 (lane & 31) + (lane >> 5) -> one 16-byte store per channel half and plane
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                if (wave + NCF_WAVES * u >= nt1) break;               // (wave-uniform) the clamped copy is not stored
+                if (hw + NCF_HWAVES * u >= nt1) break;                // (wave-uniform) the clamped copy is not stored
                 unsigned char *dst = Hs + s2dst[u];                  // (a position outside the volume: the spare slot)
 #pragma unroll
                 for (int kh = 0; kh < 2; ++kh) {
@@ -458,14 +469,14 @@ __global__ __launch_bounds__(NCF_THREADS, 2) void nc_fused_kernel(NcFusedArgs a)
             // two m-tiles at a time (independent accumulators), the fragments of step st + 1 in flight during the MFMAs of step st
             const bool yalign = (YROW & 3) == 0;               // every (slot, plane) row of the accumulators starts 16-byte aligned
             if (FIXED) {
-                // TC * P = 352 = 22 whole m-tiles: wave w takes the pairs (w + 8 i, w + 8 i + 4), i = 0 .. 2; the second tile of
+                // TC * P = 352 = 22 whole m-tiles: wave w of the half takes the pairs (w + 8 i, w + 8 i + 4), i = 0 .. 2; the second tile of
                 // the last pair does not exist for waves 2 and 3 (they multiply the first one twice and drop the copy)
                 const unsigned char *hl = Hs + row16 * 16;
                 float *yl = ydst + 4 * kb4;
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
-                    const int qa = (wave + 8 * i) * 16;
-                    const bool has_b = i < 2 || wave < 2;
+                    const int qa = (hw + 8 * i) * 16;
+                    const bool has_b = i < 2 || hw < 2;
                     const int qb = has_b ? qa + 64 : qa;
                     const unsigned char *ha = hl + qa * 16, *hb = hl + qb * 16;
                     nf4 accA = {0.f, 0.f, 0.f, 0.f}, accB = {0.f, 0.f, 0.f, 0.f};
@@ -497,8 +508,8 @@ __global__ __launch_bounds__(NCF_THREADS, 2) void nc_fused_kernel(NcFusedArgs a)
                     }
                 }
             } else
-            for (int t = wave; t < nt2; t += 2 * NCF_WAVES) {
-                const int qa = t * 16, qb = qa + NCF_WAVES * 16;
+            for (int t = hw; t < nt2; t += 2 * NCF_HWAVES) {
+                const int qa = t * 16, qb = qa + NCF_HWAVES * 16;
                 const unsigned char *ha = Hs + min(qa + row16, TC * P - 1) * 16, *hb = Hs + min(qb + row16, TC * P - 1) * 16;
                 nf4 accA = {0.f, 0.f, 0.f, 0.f}, accB = {0.f, 0.f, 0.f, 0.f};
                 // the fragments of step st + 1 are read while the six MFMAs of step st issue (order pinned by sched_barrier)
@@ -561,9 +572,9 @@ __global__ __launch_bounds__(NCF_THREADS, 2) void nc_fused_kernel(NcFusedArgs a)
     if (pending >= 0) flush(pending);
     if (nstrips > 0 && ap_last < a_hi && ap_last >= a0) flush(ap_last);      // the volume ends inside the tile: its last slice has no slice above
 #ifdef NCF_TIMING
-    if (blockIdx.x == 5 && blockIdx.y == 0 && lane == 0) {       // (overwrites a few output cells: timing builds only)
-        __syncthreads();
-        for (int i = 0; i < 8; ++i) Y[wave * 8 + i] = (float)nt_[i];
+    __syncthreads();
+    if (blockIdx.x == 5 && br == 0 && lane == 0) {       // (overwrites a few output cells: timing builds only)
+        for (int i = 0; i < 8; ++i) Y[hw * 8 + i] = (float)nt_[i];
         Y[32] = (float)nstrips;
     }
 #endif
@@ -630,8 +641,9 @@ void pack_nc_fused(const float *w1, const float *b1, const float *w2, DeviceBlob
     }
 }
 
+// the staged input (two planes) + per branch: the hidden planes (two planes x two channel halves) and three accumulator slots
 size_t nc_fused_lds_bytes(int tb, int tc, int P) {
-    return (size_t)2 * ((9 * (tc + 4) * P * 2 + 8 + 15) & ~15) + (size_t)2 * 2 * nc_hidden_slots(tc, P) * 16 + (size_t)3 * tb * nc_yrow(tc, P) * 4 + 256;
+    return (size_t)2 * nc_xplane(tc, P) + 2 * ((size_t)2 * 2 * nc_hidden_slots(tc, P) * 16 + (size_t)3 * tb * nc_yrow(tc, P) * 4);
 }
 
 // float bits of max |x| over n values per pair -> out[pair * out_stride] (zero beforehand); one atomic per work-group, <= 256
@@ -673,27 +685,47 @@ int launch_absmax(const float *x, size_t n, size_t stride, int pairs, int *out, 
     return check_launch("absmax_kernel");
 }
 
-// Tile of the fused kernel for a volume and batch: the B row in pieces of <= 60 columns; (TB, TC) = (5, 8) keeps two
-// work-groups per compute unit (78 KB of LDS each) and gives 7 + 22 well-balanced MFMA tiles per strip; the march along a is
-// split only until the launch has >= 1024 work-groups (two per compute unit, twice over).  Returns the number of work-groups.
+constexpr size_t NCF_LDS_MAX = 160 * 1024;     // of a compute unit (gfx950); a work-group may have all of it
+constexpr int NCF_SLOTS = 256;                  // work-groups in flight: one per compute unit
+
+// Tile of the fused kernel for a volume and batch: the B row in pieces of <= 60 columns, TC = 8 (7 + 22 well-balanced MFMA
+// tiles per strip and branch).  A work-group walks (ta + 2)(tb + 2) strips for ta x tb output planes, and the launch runs in
+// rounds of NCF_SLOTS work-groups: tb = 10 (b halo 1.2; all of the LDS at the fixed tile) or tb = 5 (1.4, twice the
+// work-groups), whichever gives fewer strips per compute unit; the march along a is split only while the launch does not fill
+// the compute units once.  16 pairs of 30x40x30x40 and 2 pairs of 60x80x60x80 both give (ta, tb) = (d0, 10): 256
+// work-groups, one round (tb = 8 gives 320: a second round that is three quarters empty).  Results do not depend on any of
+// it.  Returns the number of work-groups.
 static long nc_fused_tile(NcFusedArgs &a, int pairs, const int *forced) {
     const int d0 = a.d0, d1 = a.d1, d2 = a.d2, d3 = a.d3;
     a.nd = ceil_div(d3, 60);
     a.td = ceil_div(d3, a.nd);
     a.P = (a.td + 4 + 1) & ~1;
-    a.tb = 5; a.tc = 8; a.ta = 0;
-    if (forced && forced[1] > 0 && forced[2] > 0) { a.ta = forced[0]; a.tb = forced[1]; a.tc = forced[2]; }      // (ta = 0: pick)
-    a.tb = std::min(a.tb, d1); a.tc = std::min(a.tc, d2);
+    a.tc = 8;
+    const bool forced_bc = forced && forced[1] > 0 && forced[2] > 0;
+    if (forced_bc) a.tc = forced[2];
+    a.tc = std::min(a.tc, d2);
     // kernel limits: a row of <= 64 columns per wave instruction, <= 3 input rows per wave and plane, <= 2 layer-1 tiles per wave
     while (a.tc > 1 && (a.tc + 4 > 12 || (a.tc + 2) * a.P > 512)) --a.tc;
-    a.nb = ceil_div(d1, a.tb); a.nc = ceil_div(d2, a.tc);
-    if (a.ta <= 0) {
-        a.ta = d0;
-        while (a.ta > 4 && (long)ceil_div(d0, a.ta) * a.nb * a.nc * a.nd * 2 * pairs < 1024) a.ta = (a.ta + 1) / 2;
+    a.nc = ceil_div(d2, a.tc);
+    const int forced_ta = forced_bc ? forced[0] : 0;                       // (ta = 0: pick)
+    long best = -1;
+    int best_ta = 0, best_tb = 0;
+    for (int cand : {10, 5}) {
+        int tb = std::min(forced_bc ? forced[1] : cand, d1);
+        while (tb > 1 && nc_fused_lds_bytes(tb, a.tc, a.P) > NCF_LDS_MAX) --tb;
+        const long per_a = (long)ceil_div(d1, tb) * a.nc * a.nd * pairs;
+        int ta = forced_ta > 0 ? forced_ta : d0;
+        if (forced_ta <= 0)
+            while (ta > 4 && ceil_div(d0, ta) * per_a < NCF_SLOTS) ta = (ta + 1) / 2;
+        ta = std::min(ta, d0);
+        const long groups = ceil_div(d0, ta) * per_a;
+        const long cost = (groups + NCF_SLOTS - 1) / NCF_SLOTS * (ta + 2) * (tb + 2);
+        if (best < 0 || cost < best) { best = cost; best_ta = ta; best_tb = tb; }
+        if (forced_bc) break;
     }
-    a.ta = std::min(a.ta, d0);
-    a.na = ceil_div(d0, a.ta);
-    return (long)a.na * a.nb * a.nc * a.nd * 2 * pairs;
+    a.ta = best_ta; a.tb = best_tb;
+    a.na = ceil_div(d0, a.ta); a.nb = ceil_div(d1, a.tb);
+    return (long)a.na * a.nb * a.nc * a.nd * pairs;
 }
 
 int launch_nc_fused(const float *X, float *Y, float *Y2, size_t stride, int pairs, int d0, int d1, int d2, int d3,
@@ -707,15 +739,20 @@ int launch_nc_fused(const float *X, float *Y, float *Y2, size_t stride, int pair
     a.xmax = xmax; a.xmax_stride = xmax_stride;
     nc_fused_tile(a, pairs, forced_tile);
     const size_t lds = nc_fused_lds_bytes(a.tb, a.tc, a.P);
-    P2P_REQUIRE(a.P <= 64 && lds <= 160 * 1024 && a.tc + 4 <= 12 && (a.tc + 2) * a.P <= 512, P2P_EUNSUPPORTED,
+    P2P_REQUIRE(a.P <= 64 && lds <= NCF_LDS_MAX && a.tc + 4 <= 12 && (a.tc + 2) * a.P <= 512, P2P_EUNSUPPORTED,
                 "consensus tile does not fit (P %d, tc %d, LDS %zu)", a.P, a.tc, lds);
     static DeviceOnce attr_set;
-    const int dev = raise_lds_limit(attr_set, {{(const void *)nc_fused_kernel<false>, 160 * 1024}, {(const void *)nc_fused_kernel<true>, 160 * 1024}});
+    const int dev = raise_lds_limit(attr_set, {{(const void *)nc_fused_kernel<0>, (int)NCF_LDS_MAX}, {(const void *)nc_fused_kernel<5>, (int)NCF_LDS_MAX},
+                                               {(const void *)nc_fused_kernel<10>, (int)NCF_LDS_MAX}});
     if (dev < 0) return dev;
-    if (a.tb == 5 && a.tc == 8 && a.td == 40 && a.P == 44)
-        hipLaunchKernelGGL(nc_fused_kernel<true>, dim3(a.na * a.nb * a.nc * a.nd, 2, pairs), dim3(NCF_THREADS), lds, stream, a);
+    const dim3 grid(a.na * a.nb * a.nc * a.nd, 1, pairs);                  // one work-group per tile: both branches
+    const bool fixed = a.tc == 8 && a.td == 40 && a.P == 44;
+    if (fixed && a.tb == 10)
+        hipLaunchKernelGGL(nc_fused_kernel<10>, grid, dim3(NCF_THREADS), lds, stream, a);
+    else if (fixed && a.tb == 5)
+        hipLaunchKernelGGL(nc_fused_kernel<5>, grid, dim3(NCF_THREADS), lds, stream, a);
     else
-        hipLaunchKernelGGL(nc_fused_kernel<false>, dim3(a.na * a.nb * a.nc * a.nd, 2, pairs), dim3(NCF_THREADS), lds, stream, a);
+        hipLaunchKernelGGL(nc_fused_kernel<0>, grid, dim3(NCF_THREADS), lds, stream, a);
     return check_launch("nc_fused_kernel");
 }
 
