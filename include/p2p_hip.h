@@ -355,6 +355,67 @@ int p2p_epipolar_batch(const void *matches, int matches_dtype, const int *counts
                        int kind, double eps, const double *edges, int nbins, void *dist, int dist_dtype, int *hist,
                        p2p_stream_t stream);
 
+/* ---- matching operators on their own (since version 110) ------------------------------------------ */
+
+/* The pieces p2p_coarse_forward* fuses, each as an entry point of its own, for callers that build a coarse stage from the
+ * reference's operators (networks/modules.py, networks/ncn/model.py, networks/ncn/conv4d.py).  They change nothing above: the fused
+ * path keeps its kernels, its limits and its refusals.  Common to all of them: `batch` items contiguous along the leading axis,
+ * 1 <= batch <= 65535; one launch (or one per step) for the whole batch; an item's result depends on the item and the sizes
+ * alone -- every sum runs in an order the sizes fix -- so it is bit-identical alone, in any batch and in any slot.  Null pointers
+ * and non-positive sizes -> P2P_EINVAL, sizes beyond the stated limits -> P2P_EUNSUPPORTED, both before the device is touched. */
+
+/* FeatCorrelation -- reference networks/modules.py:41-53: out[b][pa][pb] = sum_c featA[b][c][pa] * featB[b][c][pb], the plain
+ * product: no L2 normalisation, no pooling.
+ *   featA [B,C,hA,wA], featB [B,C,hB,wB] -> out [B, hA*wA, hB*wB]   (the reference's '4D' and '3D' shapes are views / permutes)
+ * Any C >= 1, any sides >= 1, A and B sizes independent (hA*wA <= 65535 * 64).  Arithmetic: EXACT fp32 on the matrix cores
+ * (v_mfma_f32_16x16x4_f32, bit-identical to one fp32 fma chain over the channels in ascending order) -- not the fp16-plane
+ * scheme of the fused kernel, whose power-of-two scale relies on normalised features.  csrc/operators.hip. */
+int p2p_correlation_batch(const float *featA, const float *featB, int batch, int channels, int hA, int wA, int hB, int wB,
+                          float *out, p2p_stream_t stream);
+
+/* maxpool4d -- reference networks/modules.py:11-34 -- of a caller's volume:
+ *   x [B,H1,W1,H2,W2] -> pooled_out [B,H1/k,W1/k,H2/k,W2/k] fp32, bit-equal to torch.max over the k^4 slices (a window that
+ *   holds a NaN gives NaN and the code of its first NaN, as torch.max does);
+ *   delta_out: the same shape, uint8 (optional): s = ((i*k+j)*k+k')*k+l of the FIRST maximum in the reference's slice order
+ *   (modules.py:13-18); the unpack kernel above expands it into the reference's four int64 tensors.
+ * k: 1 to 4 (k > 4 -> P2P_EUNSUPPORTED: the codes must fit the byte); k = 3 exists here only, the fused coarse entry points keep
+ * refusing it.  Sides that are not multiples of k -> P2P_EINVAL.  One thread per pooled cell. */
+int p2p_maxpool4d_batch(const float *x, int batch, int h1, int w1, int h2, int w2, int k, float *pooled_out, uint8_t *delta_out,
+                        p2p_stream_t stream);
+
+/* MutualMatching -- reference networks/ncn/model.py:157-176 -- in the reference's parenthesisation
+ *   y = x * ((x / (maxB + 1e-5)) * (x / (maxA + 1e-5))),   maxB / maxA: the maximum over the B cells of an A cell / over the A cells of a B cell,
+ * x [B,hA,wA,hB,wB] -> y_out of the same shape (y_out == x allowed): the maxima and apply kernels of the coarse stage
+ * (csrc/coarse.hip section 3; IEEE divisions).  workspace: device memory, 4-byte aligned, the query's bytes (the maxima of every
+ * item; P2P_ENOMEM if it is missing or smaller).  The query returns 0 for bad arguments.  Three launches.  hA*wA * hB*wB < 2^31
+ * cells per item (the apply kernel indexes in 32 bits; P2P_EUNSUPPORTED beyond). */
+size_t p2p_mutual_matching_workspace_bytes(int batch, int hA, int wA, int hB, int wB);
+int p2p_mutual_matching_batch(const float *x, int batch, int hA, int wA, int hB, int wB, float *y_out, void *workspace,
+                              size_t workspace_bytes, p2p_stream_t stream);
+
+/* One Conv4d layer -- reference networks/ncn/conv4d.py:12-74, 77-130: the "same" 4-D cross-correlation with zero padding k / 2 on
+ * all four axes, plus bias; no ReLU.  HOST pointers: weight in the stored (pre-permuted, conv4d.py:119-120) layout
+ * [k, c_out, c_in, k, k, k], bias [c_out] or NULL.  c_in, c_out 1..16, kernel_size 3 or 5 (P2P_EUNSUPPORTED otherwise).
+ *   x [B,c_in,h1,w1,h2,w2] -> y_out [B,c_out,h1,w1,h2,w2]   (not in place)
+ * Arithmetic: exact fp32 on v_mfma_f32_16x16x4_f32, the layer launch of the generic consensus stack (csrc/consensus_generic.hip)
+ * reading and writing channel planes.  Every output sums its k^4 c_in terms in an order the layer alone fixes: the K axis (taps
+ * outer in the order (da, db, dc, dd), channels inner, c_in padded to 4, 8 or 16 unless it is 1) is cut into super-steps of 16
+ * values; super-step S is added, value by value, to partial sum S % 4; the result is (s0 + s1) + (s2 + s3), then + bias.  The four
+ * sums keep the rounding error at that of the reference's slice-wise convolutions; a layer of a generic consensus stack keeps ONE
+ * chain over the same K order, so a stand-alone layer and the same layer inside such a stack agree to rounding, not bit for bit.
+ * Sides may be smaller than the kernel.  Fewer than 2^31 cells. */
+typedef struct p2p_conv4d p2p_conv4d;
+int p2p_conv4d_create(const float *weight, const float *bias, int c_in, int c_out, int kernel_size, p2p_conv4d **out);
+void p2p_conv4d_destroy(p2p_conv4d *conv);
+int p2p_conv4d_forward_batch(const p2p_conv4d *conv, const float *x, int batch, int h1, int w1, int h2, int w2, float *y_out,
+                             p2p_stream_t stream);
+
+/* L2Normalize -- reference networks/modules.py:6 (eps inside the root): y = x / sqrt(sum_C x^2 + 1e-6) over the middle axis of the
+ * contiguous [outer, channels, inner] view of a tensor (dim d of a tensor: outer = the product of the sizes before d, inner = of
+ * those after it).  The squares of a position are added in ascending channel order, one fma each; IEEE square root and division.
+ * y == x allowed. */
+int p2p_l2_normalize(const float *x, size_t outer, int channels, size_t inner, float *y, p2p_stream_t stream);
+
 /* ---- fine stage ------------------------------------------------------------------------------ */
 
 /* One image's feature pyramid levels feat_idx [0,1,2,3] (reference networks/resnet.py:138-157 with

@@ -4,6 +4,7 @@
     sys.path.append('<repo>/patch2pix_amd')
     from utils.eval.model_helper import load_model, estimate_matches
     from networks.patch2pix import Patch2Pix
+    from networks.ncn.model import NeighConsensus      # any submodule, sub-packages included (networks.modules, networks.ncn.*)
 
 `networks/__init__.py` and `utils/__init__.py` notice that they are being imported under the bare name, load the real
 package (`patch2pix_amd`, by file location -- `sys.path` is not touched) and call `install()`.  From then on

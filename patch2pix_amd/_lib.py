@@ -176,6 +176,18 @@ p2p_resize_bicubic_batch = _sig("p2p_resize_bicubic_batch", ctypes.c_int,
                                 [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                  c_stream])
 
+# the matching operators on their own (version 110)
+p2p_correlation_batch = _sig("p2p_correlation_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p, c_stream])
+p2p_maxpool4d_batch = _sig("p2p_maxpool4d_batch", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_void_p, c_stream])
+p2p_mutual_matching_workspace_bytes = _sig("p2p_mutual_matching_workspace_bytes", ctypes.c_size_t, [ctypes.c_int] * 5)
+p2p_mutual_matching_batch = _sig("p2p_mutual_matching_batch", ctypes.c_int,
+                                 [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_stream])
+p2p_conv4d_create = _sig("p2p_conv4d_create", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_void_p)])
+p2p_conv4d_destroy = _sig("p2p_conv4d_destroy", None, [ctypes.c_void_p])
+p2p_conv4d_forward_batch = _sig("p2p_conv4d_forward_batch", ctypes.c_int,
+                                [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p, c_stream])
+p2p_l2_normalize = _sig("p2p_l2_normalize", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, c_stream])
+
 p2p_regressor_set_mode = _sig("p2p_regressor_set_mode", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int])
 p2p_regressor_get_mode = _sig("p2p_regressor_get_mode", ctypes.c_int, [ctypes.c_void_p])
 REGRESS_MODES = {"f32": 0, "fp16x2": 3, "fp16x2w": 4}
@@ -189,7 +201,9 @@ EXPORTS = ["p2p_version", "p2p_last_error", "p2p_ncn_create", "p2p_ncn_destroy",
            "p2p_maxpool_nhwc", "p2p_nhwc_to_nchw", "p2p_regressor_create_config", "p2p_regress_workspace_bytes_for",
            "p2p_coarse_matches_topk_batch", "p2p_ncn_create_config", "p2p_ncn_is_generic", "p2p_coarse_workspace_bytes_for",
            "p2p_neigh_consensus_workspace_bytes", "p2p_resize_workspace_bytes", "p2p_resize_bicubic_batch",
-           "p2p_coarse_score_workspace_bytes", "p2p_coarse_score_batch", "p2p_epipolar_batch"]
+           "p2p_coarse_score_workspace_bytes", "p2p_coarse_score_batch", "p2p_epipolar_batch",
+           "p2p_correlation_batch", "p2p_maxpool4d_batch", "p2p_mutual_matching_workspace_bytes", "p2p_mutual_matching_batch",
+           "p2p_conv4d_create", "p2p_conv4d_destroy", "p2p_conv4d_forward_batch", "p2p_l2_normalize"]
 
 
 def check(status, what):

@@ -14,12 +14,13 @@ void set_error(const char *fmt, ...) {
 }  // namespace p2p
 
 #ifdef P2P_EXPERIMENT
-extern "C" int p2p_version(void) { return 109 | P2P_VERSION_EXPERIMENT; }
+extern "C" int p2p_version(void) { return 110 | P2P_VERSION_EXPERIMENT; }
 #else
-extern "C" int p2p_version(void) { return 109; }
+extern "C" int p2p_version(void) { return 110; }
 #endif
 extern "C" const char *p2p_last_error(void) { return p2p::g_err; }
 
 #include "coarse_api.hip"        // coarse stage: handle, workspace, entry points
+#include "operators_api.hip"     // the matching operators on their own: argument checks, entry points
 #include "regress_api.hip"       // fine stage: handle, modes, entry points
 #include "preprocess.hip"       // bicubic resize + normalisation (kernels and their entry points; no unit of its own)

@@ -553,7 +553,8 @@ void launch_mm_apply(const float *X, int nA, int nB, const int *rkey, const int 
 
 }  // namespace p2p
 
-// sections 4 (its shape-generic part), 5 and 6: no units of their own
+// sections 4 (its shape-generic part), 5 and 6, and the stand-alone operators: no units of their own
 #include "consensus_generic.hip"
 #include "matches.hip"
 #include "score.hip"
+#include "operators.hip"

@@ -66,6 +66,33 @@ size_t nc_generic_ws_bytes(const NcGen &g, size_t cells);
 int launch_nc_generic(const NcGen &g, const float *X, size_t s_x, float *Y, size_t s_y, float *act, size_t s_act, int pairs,
                       int d0, int d1, int d2, int d3, hipStream_t stream);
 
+// one stand-alone Conv4d layer (p2p_conv4d_*): the PLANAR form of the generic kernel (Conv4dLayer: defined there)
+struct Conv4dLayer;
+int conv4d_create(const float *weight, const float *bias, int c_in, int c_out, int k, Conv4dLayer **out);
+void conv4d_destroy(Conv4dLayer *h);
+void conv4d_dims(const Conv4dLayer &h, int *c_in, int *c_out);
+int launch_conv4d(const Conv4dLayer &h, const float *x, float *y, int pairs, int d0, int d1, int d2, int d3, hipStream_t stream);
+
+// ---- operators.hip: the matching operators as entry points of their own -----------------------------------------------------
+struct CorrelationArgs {
+    const float *A, *B;      // [item][C][nA], [item][C][nB]
+    float *out;              // [item][nA][nB]
+    int C, nA, nB;
+    size_t sA, sB, sOut;     // floats between items
+};
+void launch_correlation(const CorrelationArgs &a, int batch, hipStream_t stream);
+struct MaxPool4dArgs {
+    const float *x;          // [item][p0 k][p1 k][p2 k][p3 k]
+    float *pooled;           // [item][p0][p1][p2][p3]
+    uint8_t *code;           // the same shape; optional
+    int k, p1, p2, p3;
+    size_t cells;            // pooled cells per item
+};
+void launch_maxpool4d(const MaxPool4dArgs &a, int batch, hipStream_t stream);
+void launch_l2_normalize(const float *x, size_t outer, int C, size_t inner, float *y, hipStream_t stream);
+// keys: per item sKeys = roundup4(nA) + roundup4(nB) words (row keys, then column keys)
+void launch_mutual_matching(const float *x, int nA, int nB, float *y, int *keys, size_t sKeys, int batch, hipStream_t stream);
+
 }  // namespace p2p
 
 // The opaque handle of include/p2p_hip.h: the fused kernel's weights or a generic stack.  `delete` frees either.
@@ -75,4 +102,10 @@ struct p2p_ncn {
     int tile[3];             // forced (ta, tb, tc) of the fused kernel, 0 = automatic (p2p_ncn_set_tile: tests and sweeps)
     p2p::NcGen *gen;         // a generic handle (p2p_ncn_create_config): its layers; the fields above are unused then
     ~p2p_ncn() { p2p::nc_generic_destroy(gen); }
+};
+
+// One Conv4d layer (p2p_conv4d_create)
+struct p2p_conv4d {
+    p2p::Conv4dLayer *layer;
+    ~p2p_conv4d() { p2p::conv4d_destroy(layer); }
 };

@@ -55,12 +55,16 @@ struct NcGenArgs {
     int k, cpi, cpo, nsteps;
     int tiles;               // per pair
     int add;                 // last layer of the transposed branch: out += result
+    int ci;                  // PLANAR only: the real input channels (channel ch of a cell sits ch * cells floats further on)
+    size_t cells;            // PLANAR only: cells of the volume = floats between two channel planes
 };
 
 __device__ __forceinline__ int ncg_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // FIRST: the layer reads the caller's one-channel volume (cpi == 1)
-template <bool FIRST>
+// PLANAR: one stand-alone Conv4d layer (p2p_conv4d_*, conv4d.py:12-74) on the caller's tensors: input [pair][ci][cells] and
+// output [pair][co][cells] channel-major as PyTorch lays them out, bias, NO ReLU; the K order is the one of the stack's layers
+template <bool FIRST, bool PLANAR>
 __global__ __launch_bounds__(256) void nc_generic_kernel(NcGenArgs a) {
     __shared__ int taps[NCG_MAX_TAPS];       // (da, db, dc, dd) of a tap, one byte each; taps past the last repeat it (zero weights)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -92,9 +96,11 @@ __global__ __launch_bounds__(256) void nc_generic_kernel(NcGenArgs a) {
         return (size_t)((ncg_clamp(ia, a.d0 - 1) * a.d1 + ncg_clamp(ib, a.d1 - 1)) * a.d2 + ncg_clamp(ic, a.d2 - 1)) * a.d3 + ncg_clamp(id, a.d3 - 1);
     };
 
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (FIRST) {
-        for (int S = 0; S < a.nsteps; ++S) {
+    // one super-step of the K axis into `acc` (FIRST: sixteen taps of the one input channel; else tps taps x cpi channels)
+    const int Q = FIRST ? 1 : a.cpi >> 2, tps = 4 / Q;           // quads of channels per cell; taps per super-step
+    const int tsub = kb / Q, coff = 4 * (kb - tsub * Q);
+    auto step = [&](int S, f32x4 &acc) {
+        if (FIRST) {
             f32x4 av;
             bool ok[4];
 #pragma unroll
@@ -102,18 +108,40 @@ __global__ __launch_bounds__(256) void nc_generic_kernel(NcGenArgs a) {
             const f32x4 bv = *(const f32x4 *)(wl + (size_t)S * 256);
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc = P2P_NCG_MFMA(ok[j] ? av[j] : 0.f, bv[j], acc);
-        }
-    } else {
-        const int Q = a.cpi >> 2, tps = 4 / Q;                   // quads of channels per cell; taps per super-step
-        const int tsub = kb / Q, coff = 4 * (kb - tsub * Q);
-        for (int S = 0; S < a.nsteps; ++S) {
+        } else {
             bool ok;
             const size_t cell = locate(tps * S + tsub, &ok);
-            const f32x4 ld = *(const f32x4 *)(in + cell * a.cpi + coff);
+            f32x4 ld;
+            if constexpr (PLANAR) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {      // channels past the last one: a clamped plane, zero selected
+                    const float v = in[(size_t)min(coff + j, a.ci - 1) * a.cells + cell];
+                    ld[j] = coff + j < a.ci ? v : 0.f;
+                }
+            } else {
+                ld = *(const f32x4 *)(in + cell * a.cpi + coff);
+            }
             const f32x4 bv = *(const f32x4 *)(wl + (size_t)S * 256);
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc = P2P_NCG_MFMA(ok ? ld[j] : 0.f, bv[j], acc);
         }
+    };
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (PLANAR) {
+        // four partial sums, super-step S into sum S % 4, then (s0 + s1) + (s2 + s3): the rounding error of a stand-alone layer
+        // grows with a quarter of the K axis, as that of the reference's slice-wise convolutions does
+        f32x4 part[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) part[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int S = 0; S < a.nsteps; S += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (S + u < a.nsteps) step(S + u, part[u]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = (part[0][r] + part[1][r]) + (part[2][r] + part[3][r]);
+    } else {
+        for (int S = 0; S < a.nsteps; ++S) step(S, acc);
     }
     // accumulator register r = cell dt0 + 4 kb + r of the row, column l15 = output channel
     if (l15 >= a.cpo) return;
@@ -123,6 +151,10 @@ __global__ __launch_bounds__(256) void nc_generic_kernel(NcGenArgs a) {
     for (int r = 0; r < 4; ++r) {
         const int od = dt0 + 4 * kb + r;
         if (od >= a.d3) continue;
+        if constexpr (PLANAR) {
+            out[(size_t)l15 * a.cells + row0 + od] = acc[r] + bias;
+            continue;
+        }
         float *dst = out + (row0 + od) * a.cpo + l15;
         const float v = fmaxf(acc[r] + bias, 0.f);
         *dst = a.add ? *dst + v : v;
@@ -240,12 +272,65 @@ int launch_nc_generic(const NcGen &g, const float *X, size_t s_x, float *Y, size
             a.w = L.w[br]; a.bias = L.bias;
             a.k = L.k; a.cpi = L.cpi; a.cpo = L.cpo; a.nsteps = L.nsteps;
             a.add = last && br == 1;
-            if (i == 0) hipLaunchKernelGGL(nc_generic_kernel<true>, grid, dim3(256), 0, stream, a);
-            else hipLaunchKernelGGL(nc_generic_kernel<false>, grid, dim3(256), 0, stream, a);
+            if (i == 0) hipLaunchKernelGGL((nc_generic_kernel<true, false>), grid, dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL((nc_generic_kernel<false, false>), grid, dim3(256), 0, stream, a);
             const int st = check_launch("nc_generic_kernel");
             if (st != P2P_OK) return st;
         }
     return P2P_OK;
+}
+
+// ---- one stand-alone Conv4d layer (p2p_conv4d_*): the same packing and the same kernel, PLANAR -----------------------------------
+struct Conv4dLayer {
+    NcGenLayer L;
+    DeviceBlob mem;
+};
+
+int conv4d_create(const float *weight, const float *bias, int c_in, int c_out, int k, Conv4dLayer **out) {
+    Conv4dLayer *h = new Conv4dLayer();
+    NcGenLayer &L = h->L;
+    L.k = k; L.ci = c_in; L.co = c_out;
+    L.cpi = c_in == 1 ? 1 : ncg_pad_channels(c_in);
+    L.cpo = c_out;
+    const int ntap = k * k * k * k;
+    L.nsteps = ceil_div(ntap * L.cpi, 16);
+    const size_t o_w = h->mem.take<float>((size_t)L.nsteps * 256), o_b = h->mem.take<float>(16);
+    float *host = h->mem.at<float>(0);
+    gen_nc_pack(weight, L, c_in == 1, 0, &host[o_w]);
+    for (int q = 0; q < c_out; ++q) host[o_b + q] = bias ? bias[q] : 0.f;
+    const int st = h->mem.upload("p2p_conv4d_create: the packed filters");
+    if (st != P2P_OK) {
+        delete h;
+        return st;
+    }
+    L.w[0] = h->mem.dev<float>(o_w); L.w[1] = nullptr;
+    L.bias = h->mem.dev<float>(o_b);
+    *out = h;
+    return P2P_OK;
+}
+
+void conv4d_destroy(Conv4dLayer *h) { delete h; }
+void conv4d_dims(const Conv4dLayer &h, int *c_in, int *c_out) { *c_in = h.L.ci; *c_out = h.L.co; }
+
+// x [pairs][ci][cells] -> y [pairs][co][cells]
+int launch_conv4d(const Conv4dLayer &h, const float *x, float *y, int pairs, int d0, int d1, int d2, int d3, hipStream_t stream) {
+    P2P_REQUIRE((unsigned long long)d0 * d1 * d2 * d3 < (1ull << 31), P2P_EUNSUPPORTED,
+                "p2p_conv4d_forward: volume %d x %d x %d x %d has 2^31 cells or more", d0, d1, d2, d3);
+    const NcGenLayer &L = h.L;
+    NcGenArgs a{};
+    a.cells = (size_t)d0 * d1 * d2 * d3;
+    a.d0 = d0; a.d1 = d1; a.d2 = d2; a.d3 = d3; a.nd = ceil_div(d3, 16);
+    const long long tiles = (long long)d0 * d1 * d2 * a.nd;
+    P2P_REQUIRE(tiles < (1ll << 31) - 4, P2P_EUNSUPPORTED, "p2p_conv4d_forward: %lld row tiles in one launch", tiles);
+    a.tiles = (int)tiles;
+    a.in = x; a.s_in = a.cells * L.ci;
+    a.out = y; a.s_out = a.cells * L.co;
+    a.w = L.w[0]; a.bias = L.bias;
+    a.k = L.k; a.cpi = L.cpi; a.cpo = L.cpo; a.nsteps = L.nsteps; a.ci = L.ci;
+    const dim3 grid((unsigned)((tiles + 3) / 4), 1, (unsigned)pairs);
+    if (L.ci == 1) hipLaunchKernelGGL((nc_generic_kernel<true, true>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((nc_generic_kernel<false, true>), grid, dim3(256), 0, stream, a);
+    return check_launch("nc_generic_kernel (Conv4d)");
 }
 
 }  // namespace p2p

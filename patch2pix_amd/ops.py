@@ -513,6 +513,8 @@ def neigh_consensus_batch(x, ncn):
 def delta_unpack(delta, ksize):
     """Packed argmax byte -> the reference's (max_i, max_j, max_k, max_l) int64 tensors."""
     out = torch.empty((4,) + tuple(delta.shape), dtype=torch.int64, device=delta.device)
+    if delta.numel() == 0:
+        return out[0], out[1], out[2], out[3]
     with torch.cuda.device(delta.device):
         _lib.check(_lib.p2p_delta_unpack(delta.data_ptr(), delta.numel(), ksize, out.data_ptr(), _stream()),
                    "p2p_delta_unpack")
@@ -904,3 +906,122 @@ def regress_batch(reg1, reg2, pyrs1, pyrs2, proposals, want_mid=True, want_raw=F
 def regress(reg1, reg2, pyr1, pyr2, proposals, want_mid=True, want_raw=False):
     """Single-pair form of regress_batch (returns one dict)."""
     return regress_batch(reg1, reg2, [pyr1], [pyr2], [proposals], want_mid, want_raw)[0]
+
+
+# ---- the matching operators on their own (networks.modules, networks.ncn.*) -------------------------------------------------
+def _op_input(t, name, dim=None):
+    """Inference only, on the GPU: what every operator front end asks of an input tensor."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be on the GPU (got {t.device}): the operators have no CPU path")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32 (got {t.dtype})")
+    if t.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f"{name} requires grad: the operators are inference only (wrap the call in torch.no_grad())")
+    if dim is not None and t.dim() != dim:
+        raise ValueError(f"{name} must have {dim} dimensions (got {tuple(t.shape)})")
+    return t.detach().contiguous()
+
+
+def correlation_batch(feat_a, feat_b):
+    """FeatCorrelation (modules.py:41-53): feat_a [B,C,hA,wA], feat_b [B,C,hB,wB] -> [B, hA*wA, hB*wB], exact fp32 MFMA."""
+    feat_a, feat_b = _op_input(feat_a, "feat1", 4), _op_input(feat_b, "feat2", 4)
+    if feat_a.shape[:2] != feat_b.shape[:2] or feat_a.device != feat_b.device:
+        raise ValueError(f"feature maps {tuple(feat_a.shape)} and {tuple(feat_b.shape)} must agree in batch, channels and device")
+    nb, c, ha, wa = feat_a.shape
+    hb, wb = feat_b.shape[2:]
+    out = torch.empty((nb, ha * wa, hb * wb), dtype=torch.float32, device=feat_a.device)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(feat_a.device):
+        _lib.check(_lib.p2p_correlation_batch(feat_a.data_ptr(), feat_b.data_ptr(), nb, c, ha, wa, hb, wb, out.data_ptr(), _stream()),
+                   "p2p_correlation_batch")
+    return out
+
+
+def maxpool4d_batch(x, k, want_delta=True):
+    """maxpool4d (modules.py:11-34) of x [B,H1,W1,H2,W2] -> (pooled [B,H1/k,...], packed delta uint8 of that shape or None)."""
+    x = _op_input(x, "corr4d_hres", 5)
+    nb, h1, w1, h2, w2 = x.shape
+    k = int(k)
+    shape = (nb, h1 // k, w1 // k, h2 // k, w2 // k) if k > 0 else (nb, 0, 0, 0, 0)
+    pooled = torch.empty(shape, dtype=torch.float32, device=x.device)
+    delta = torch.empty(shape, dtype=torch.uint8, device=x.device) if want_delta else None
+    if x.numel() == 0 and k > 0:
+        return pooled, delta
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.p2p_maxpool4d_batch(x.data_ptr(), nb, h1, w1, h2, w2, k, pooled.data_ptr(),
+                                            delta.data_ptr() if want_delta else None, _stream()), "p2p_maxpool4d_batch")
+    return pooled, delta
+
+
+def mutual_matching_batch(x):
+    """MutualMatching (ncn/model.py:157-176) of x [B,hA,wA,hB,wB] -> the same shape."""
+    x = _op_input(x, "corr4d", 5)
+    nb, ha, wa, hb, wb = x.shape
+    y = torch.empty_like(x)
+    if x.numel() == 0:
+        return y
+    with torch.cuda.device(x.device):
+        nbytes = _lib.p2p_mutual_matching_workspace_bytes(nb, ha, wa, hb, wb)
+        ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=x.device)
+        _lib.check(_lib.p2p_mutual_matching_batch(x.data_ptr(), nb, ha, wa, hb, wb, y.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+                   "p2p_mutual_matching_batch")
+    return y
+
+
+def l2_normalize(x, dim):
+    """L2Normalize (modules.py:6) of x along `dim`."""
+    x = _op_input(x, "feat")
+    dim = dim % x.dim()
+    outer, c, inner = math.prod(x.shape[:dim]), x.shape[dim], math.prod(x.shape[dim + 1:])
+    y = torch.empty_like(x)
+    if x.numel() == 0:
+        return y
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.p2p_l2_normalize(x.data_ptr(), outer, c, inner, y.data_ptr(), _stream()), "p2p_l2_normalize")
+    return y
+
+
+class Conv4dWeights:
+    """Device-resident filters of one Conv4d layer (conv4d.py:77-130): weight in the stored layout [k, c_out, c_in, k, k, k]."""
+
+    def __init__(self, weight, bias, device):
+        w = _host(weight)
+        if w.dim() != 6 or len({w.shape[0], w.shape[3], w.shape[4], w.shape[5]}) != 1:
+            raise ValueError(f"Conv4d weight has shape {tuple(w.shape)}: expected the stored layout [k, c_out, c_in, k, k, k]")
+        b = _host(bias) if bias is not None else None
+        if b is not None and tuple(b.shape) != (w.shape[1],):
+            raise ValueError(f"Conv4d bias has shape {tuple(b.shape)}: expected ({w.shape[1]},)")
+        self.c_in, self.c_out, self.k = int(w.shape[2]), int(w.shape[1]), int(w.shape[0])
+        self.handle = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(_lib.p2p_conv4d_create(w.data_ptr(), b.data_ptr() if b is not None else None, self.c_in, self.c_out, self.k,
+                                              ctypes.byref(self.handle)), "p2p_conv4d_create")
+        self.device = torch.device(device)
+
+    def __del__(self):
+        if getattr(self, "handle", None) and _lib is not None:
+            _lib.p2p_conv4d_destroy(self.handle)
+            self.handle = None
+
+
+def conv4d_forward_batch(x, conv):
+    """One Conv4d layer: x [B,c_in,h1,w1,h2,w2] -> [B,c_out,h1,w1,h2,w2] (bias, no ReLU), exact fp32 MFMA."""
+    x = _op_input(x, "data", 6)
+    nb, c, h1, w1, h2, w2 = x.shape
+    if c != conv.c_in:
+        raise ValueError(f"data has {c} channels, the layer takes {conv.c_in}")
+    y = torch.empty((nb, conv.c_out, h1, w1, h2, w2), dtype=torch.float32, device=x.device)
+    if y.numel() == 0:
+        return y
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.p2p_conv4d_forward_batch(conv.handle, x.data_ptr(), nb, h1, w1, h2, w2, y.data_ptr(), _stream()),
+                   "p2p_conv4d_forward_batch")
+    return y
+
+
+def tensor_signature(tensors):
+    """Identity, version counter and storage of every tensor: the key of a packed-weights cache (ResNet34._hip_signature)."""
+    return tuple((id(t), t._version, t.data_ptr(), tuple(t.shape), str(t.device)) for t in tensors)
