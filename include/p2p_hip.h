@@ -112,13 +112,19 @@ void p2p_regressor_destroy(p2p_regressor *reg);
  *                      Winograd F(2x2, 3x3): 16 batched GEMMs over the transformed tiles of ALL proposals (2.25x fewer
  *                      matrix-core passes; the transforms are exact up to fp32 rounding, transformed filters computed in
  *                      fp64 at pack time) -- three launches per regressor level instead of one, and a larger scratch
- *                      buffer (the transformed conv2 input of a chunk of up to 3328 proposals, 512 KiB each).
+ *                      buffer (the transformed conv2 input of a chunk of up to 3328 proposals, 512 KiB each);
+ *   P2P_REGRESS_FP16   (opt-in, since version 111; NOT fp32-equivalent) the structure of P2P_REGRESS_FP16X2W with ONE fp16
+ *                      number per operand -- fp16(x * 2^s) under the same power-of-two scales -- and ONE
+ *                      v_mfma_f32_32x32x16_f16 per product, fp32 accumulation: a third of the matrix-core passes, half the
+ *                      operand bytes, relative operand rounding 2^-11.  Its results are NOT held to the 1e-3 px / 1e-5 bars
+ *                      of the other modes (measured error: DESIGN.md section 4, "Single-plane mode").  Tuned handles only.
  * New handles start in P2P_REGRESS_DEFAULT (the library reads no environment variables; the Python host layer maps
  * P2P_REGRESS_MODE onto p2p_regressor_set_mode).  Only the weight stream of the mode in use is packed and uploaded;
  * p2p_regressor_set_mode builds another mode's on its first selection (host-side packing + one upload).   */
 #define P2P_REGRESS_F32     0
 #define P2P_REGRESS_FP16X2  3
 #define P2P_REGRESS_FP16X2W 4
+#define P2P_REGRESS_FP16    5
 #define P2P_REGRESS_DEFAULT P2P_REGRESS_FP16X2W
 int p2p_regressor_set_mode(p2p_regressor *reg, int mode);
 int p2p_regressor_get_mode(const p2p_regressor *reg);
@@ -445,6 +451,7 @@ size_t p2p_regress_workspace_bytes(int n);
  * P2P_REGRESS_FP16X2W  4 KB per proposal slot + 512 KiB per proposal of a chunk of at most 3328 (<= 1.74 GB: the value
  *                      jumps from ~2 MB per proposal to that cap once n exceeds one chunk -- callers that run another
  *                      mode should size their buffer with this query, not with p2p_regress_workspace_bytes),
+ * P2P_REGRESS_FP16     the same with 256 KiB per proposal of a chunk (never more than P2P_REGRESS_FP16X2W),
  * P2P_REGRESS_FP16X2   4 KB per proposal slot,   P2P_REGRESS_F32   0 (the buffer is ignored).                      */
 size_t p2p_regress_workspace_bytes_mode(int n, int mode);
 /* The same for ONE handle.  Tuned handles: the value of p2p_regress_workspace_bytes_mode for the handle's mode.  Generic

@@ -190,7 +190,9 @@ p2p_l2_normalize = _sig("p2p_l2_normalize", ctypes.c_int, [ctypes.c_void_p, ctyp
 
 p2p_regressor_set_mode = _sig("p2p_regressor_set_mode", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int])
 p2p_regressor_get_mode = _sig("p2p_regressor_get_mode", ctypes.c_int, [ctypes.c_void_p])
-REGRESS_MODES = {"f32": 0, "fp16x2": 3, "fp16x2w": 4}
+REGRESS_MODES = {"f32": 0, "fp16x2": 3, "fp16x2w": 4}      # the fp32-equivalent modes
+REGRESS_MODES_LOSSY = {"fp16": 5}     # P2P_REGRESS_FP16: opt-in, one fp16 plane per operand (not fp32-equivalent; kept apart from
+                                      # the dict above, whose modes share the accuracy bars and the two-plane buffer layouts)
 REGRESS_GENERIC = 16          # P2P_REGRESS_GENERIC: the mode id of a handle made by p2p_regressor_create_config
 FEAT_COMB = {"pre": 0, "post": 1}
 

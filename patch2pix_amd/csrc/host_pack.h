@@ -92,6 +92,10 @@ static inline void split_fp16_planes(float v, uint16_t *hi, uint16_t *lo) {
     *lo = __builtin_bit_cast(uint16_t, (_Float16)(v - (float)h));
 }
 
+// fp32 -> ONE fp16 (round to nearest even): the single-plane operand of P2P_REGRESS_FP16, relative error <= 2^-11 inside the
+// normal range of fp16
+static inline uint16_t round_fp16(float v) { return __builtin_bit_cast(uint16_t, (_Float16)v); }
+
 // the exponent t for which mx * 2^t lies in [2^(target-1), 2^target): with target 12 the exact scaling that brings a channel's
 // largest weight magnitude mx to the top of the fp16 range the planes resolve (undone in the folded BatchNorm scale); 0 for a
 // channel of zeros or with a non-finite weight

@@ -20,6 +20,7 @@ static const ModeDesc MODES[P2P_REGRESS_NMODES] = {
     {P2P_REGRESS_F32, [](size_t) -> size_t { return 0; }, launch_regress_f32},
     {P2P_REGRESS_FP16X2, regress_ws_base_floats, launch_regress_h2},
     {P2P_REGRESS_FP16X2W, regress_ws_floats, launch_regress_wino},
+    {P2P_REGRESS_FP16, regress_ws_floats_fp16, fp16x1::launch_regress_wino},
 };
 // row of MODES (= slot of the handle's stream[] and view[]), -1 for an unknown mode
 static int mode_index(int mode) {
@@ -57,6 +58,15 @@ static int ensure_mode(p2p_regressor *r, int mode) {
         fold_exponent(bn1s, t1.data(), 12, b.at<float>(ob1));
         fold_exponent(bn2s, t2.data(), 0, b.at<float>(ob2));
         what = "the fp16x2 weight streams";
+    } else if (mode == P2P_REGRESS_FP16) {
+        // the structure of P2P_REGRESS_FP16X2W with one fp16 plane per operand: half the bytes of both streams
+        const size_t o2 = take(&RegDev::ww2, WW2_FLOATS_FP16), ob2 = take(&RegDev::bn2s_w, 512);
+        const size_t o1 = take(&RegDev::wh1, WH1_FLOATS_FP16), ob1 = take(&RegDev::bn1s_h, 512);
+        fp16x1::pack_wino_weights(c2, b.at<float>(o2), t2.data());
+        fp16x1::pack_h2_weights(c1, nullptr, b.at<float>(o1), nullptr, t1.data(), nullptr);
+        fold_exponent(bn1s, t1.data(), 12, b.at<float>(ob1));
+        fold_exponent(bn2s, t2.data(), 0, b.at<float>(ob2));
+        what = "the single-plane Winograd filter blocks and conv1's stream";
     } else {
         // conv2 as Winograd filter blocks + conv1's fp16x2 stream (the same stream the direct mode runs, packed here on its own:
         // the direct mode's conv2 stream -- 9.6 MB per regressor -- is neither packed nor uploaded for this mode)

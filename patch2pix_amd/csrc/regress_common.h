@@ -86,6 +86,11 @@ static inline size_t regress_ws_floats(size_t n) {
     return wino_u_offset_floats(n) + (size_t)16 * (wino_chunk_rows(n) / 8) * 16 * (WINO_BLK / 4);
 }
 
+// P2P_REGRESS_FP16 (one fp16 plane per operand): the same carve-up with half the bytes per block of the transformed input
+static inline size_t regress_ws_floats_fp16(size_t n) {
+    return wino_u_offset_floats(n) + (size_t)16 * (wino_chunk_rows(n) / 8) * 16 * (WINO_BLK / 2 / 4);
+}
+
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // extent of pyramid level j for an image extent `dim`: the backbone's strided convolutions / pooling round UP
@@ -380,6 +385,17 @@ constexpr size_t WW2_FLOATS = (size_t)16 * 4 * 16 * (WINO_BLK / 4);
 void pack_wino_weights(const float *conv2_w, float *ww2, int *t2);                // host
 int launch_regress_wino(const RegressArgs &a, int n, hipStream_t stream);
 
+// The single-plane pass of regress_h2.hip / regress_wino.hip (each file includes itself once more with one fp16 plane per operand,
+// into this namespace): mode P2P_REGRESS_FP16.  Units and blocks hold half the bytes of their two-plane counterparts.
+constexpr size_t WH1_FLOATS_FP16 = WH1_FLOATS / 2;
+constexpr size_t WW2_FLOATS_FP16 = WW2_FLOATS / 2;
+namespace fp16x1 {
+void pack_h2_weights(const float *conv1_w, const float *conv2_w, float *wh1, float *wh2, int *t1, int *t2);      // conv1 only (conv2_w null)
+int launch_regress_h2_conv1(const RegressArgs &a, int n, hipStream_t stream);
+void pack_wino_weights(const float *conv2_w, float *ww2, int *t2);
+int launch_regress_wino(const RegressArgs &a, int n, hipStream_t stream);
+}  // namespace fp16x1
+
 // ---- regress_generic.hip: the shape-generic regressor (exact fp32 MFMA, one launch per layer over a chunk of proposals) ----
 // Every configuration FeatRegressNet can express within the limits of include/p2p_hip.h (p2p_regressor_config).  A call's
 // proposal slots are cut into chunks; a chunk's activations live in the caller's workspace as fp32 [sample][y][x][channel]
@@ -442,10 +458,10 @@ __device__ __forceinline__ float regress_parse_one(float s, int o, float base, c
 
 // The opaque handle of include/p2p_hip.h.  A mode's kernels see the regressor through ONE RegDev: `common` (the BatchNorm / FC
 // pointers into `dev`, every stream pointer null) plus the stream pointers of that mode's own blob.  `delete` frees everything.
-constexpr int P2P_REGRESS_NMODES = 3;
+constexpr int P2P_REGRESS_NMODES = 4;
 struct p2p_regressor {
     int device = 0;    // the device the handle was created on: every later allocation (another mode's weight stream) goes there
-    int mode = 0;      // P2P_REGRESS_F32 | P2P_REGRESS_FP16X2 | P2P_REGRESS_FP16X2W (tuned handles), P2P_REGRESS_GENERIC (generic ones)
+    int mode = 0;      // P2P_REGRESS_F32 | P2P_REGRESS_FP16X2 | P2P_REGRESS_FP16X2W | P2P_REGRESS_FP16 (tuned handles), P2P_REGRESS_GENERIC (generic ones)
     p2p::DeviceBlob dev;                            // BatchNorm folds + FC layers (every mode)
     p2p::DeviceBlob stream[P2P_REGRESS_NMODES];     // a mode's convolution weights in its kernels' stream order (+ the BatchNorm scales with
                                                     // its exponents folded in); packed and uploaded on the mode's first selection

@@ -68,14 +68,34 @@
 // P2P_REGRESS_FP16X2W (regress_wino.hip): one level, a chunk of the proposals, gather + conv1 exactly as above, and then --
 // instead of conv2 -- the Winograd input transform B^T d B of H = BN1(conv1), written to global memory in the block layout
 // the GEMM kernel copies into LDS; the gather of the work-group's next proposal is in flight during that write-out.
+//
+// Single-plane pass.  This file compiles twice: as written (XNPL 2, everything above), and once more -- it includes itself at its
+// end -- with XNPL 1 into namespace p2p::fp16x1: the conv1 launch of mode P2P_REGRESS_FP16 (regress_wino.hip does the same for
+// the GEMM).  There every operand is ONE fp16 number, fp16(x * 2^s) under the same scales, and a product is ONE MFMA: relative
+// operand error 2^-11 instead of 2^-24 ("Single-plane mode").  Everything that differs is a macro or an
+// `#if XNPL` block, so the two-plane pass sees the token stream it always saw (NOTES.md, "regress_h2.hip de-duplication").
+#ifndef XNPL
 #define XNPL 2                          // planes per operand; XUB = bytes of a weight unit per wave (XNPL x 1 KiB)
+#endif
 #include "regress_common.h"
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+// XNS(f): a function this file defines in both passes, called with arguments of p2p's types (argument-dependent lookup would
+// find the two-plane one as well)
+#undef XNS
+#if XNPL == 1
+#define XNS(f) fp16x1::f
+#else
+#define XNS(f) f
+#endif
+
 namespace p2p {
+#if XNPL == 1
+namespace fp16x1 {
+#endif
 
 // XNPL planes per operand, XNPROD MFMA products per fp32 product, XUB bytes of a weight unit (XNPL x 1 KiB per wave)
 typedef _Float16 xe8 __attribute__((ext_vector_type(8)));
@@ -141,7 +161,14 @@ constexpr int HST = 128 * 2 + 16, HPL = 66 * HST;                 // 272, 17952
 constexpr int HCHUNK = XNPL * HPL;                                // 35904: planes of chunk c start at c * HCHUNK
 constexpr int XCONV2B = 4 * HCHUNK;
 // both phases, then the FC batch of the level (fc_batch_parse) over the whole allocation
+constexpr int HWST = 512 * 4 + 16;                                 // WINO: a pixel row of H = BN1(conv1) as fp32, [512 ch (+16 B)]
+#if XNPL == 2
 constexpr int XSM_MISC = (XCONV1B > XCONV2B) ? XCONV1B : XCONV2B;  // [16] floats, the MISC_* slots below
+#else                                   // one plane halves the conv1 operands: the fp32 H the Winograd transform reads (64 pixel
+                                        // rows + one of zeros) sets the size
+constexpr int XSM_MISC = (XCONV1B > 65 * HWST) ? XCONV1B : 65 * HWST;
+#endif
+constexpr int XWBLK = XNPL * (WINO_BLK / 2);                       // an A block of the Winograd GEMM: [plane][row 128][32 K] fp16
 #ifdef P2P_X3_TIMING
 constexpr int XSM_BYTES = XSM_MISC + 16 * 4 + 8 * 16 * 4;
 #else
@@ -165,11 +192,16 @@ __device__ __forceinline__ float pk_lo(unsigned h) { return (float)__builtin_bit
 __device__ __forceinline__ float pk_hi(unsigned h) { return (float)__builtin_bit_cast(xe2, h)[1]; }
 // v = p0 + p1: the planes of one value, stored plane_stride bytes apart
 __device__ __forceinline__ void store_planes(unsigned char *dst, int plane_stride, float v) {
+#if XNPL == 2
     const unsigned short p0 = f2e(v);
     const float r1 = v - e2f(p0);
     const unsigned short p1 = f2e(r1);
     *(unsigned short *)dst = p0;
     *(unsigned short *)(dst + plane_stride) = p1;
+#else
+    (void)plane_stride;
+    *(unsigned short *)dst = f2e(v);
+#endif
 }
 
 // 8 consecutive K values of one row (two 16-byte LDS reads), scaled by s, as XNPL planes of 8 elements
@@ -178,11 +210,15 @@ __device__ __forceinline__ void splitn(const f32x4 &xa, const f32x4 &xb, float s
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const unsigned h = pk_e(x[2 * q], x[2 * q + 1]);
+#if XNPL == 2
         const float r0 = x[2 * q] - pk_lo(h);
         const float r1 = x[2 * q + 1] - pk_hi(h);
         const unsigned m = pk_e(r0, r1);
         p[0][q] = __uint_as_float(h);
         p[1][q] = __uint_as_float(m);
+#else
+        p[0][q] = __uint_as_float(h);
+#endif
     }
 }
 
@@ -219,11 +255,19 @@ __device__ __forceinline__ void splitn(const f32x4 &xa, const f32x4 &xb, float s
       _Pragma("unroll") for (int q_ = 0; q_ < XNPL; ++q_) BUF[q_] = *(const f32x4 *)((wb + wo_) + wlane + q_ * 1024); }
 // 12 MFMAs of one m-tile (planes SP) against the weights of both n-tiles: 6 products each, smallest terms first;
 // the two accumulators alternate.  XHALFZ starts the two accumulators from zero.
+#if XNPL == 2
 #define XNPROD 3
 #define XHALF_(C0IN, C1IN, CU0, CU1, SP, BU0, BU1)                                       \
     CU0 = XMFMA(SP[1], BU0[0], C0IN); CU1 = XMFMA(SP[1], BU1[0], C1IN);                  \
     CU0 = XMFMA(SP[0], BU0[1], CU0); CU1 = XMFMA(SP[0], BU1[1], CU1);                    \
     CU0 = XMFMA(SP[0], BU0[0], CU0); CU1 = XMFMA(SP[0], BU1[0], CU1);
+#else                                   // single plane: one product
+#undef XNPROD
+#undef XHALF_
+#define XNPROD 1
+#define XHALF_(C0IN, C1IN, CU0, CU1, SP, BU0, BU1)                                       \
+    CU0 = XMFMA(SP[0], BU0[0], C0IN); CU1 = XMFMA(SP[0], BU1[0], C1IN);
+#endif
 #define XNM (2 * XNPROD)                /* MFMAs of one m-tile against both n-tiles of a slab */
 #define XHALF(CU0, CU1, SP, BU0, BU1) XHALF_(CU0, CU1, CU0, CU1, SP, BU0, BU1)
 #define XHALFZ(CU0, CU1, SP, BU0, BU1) XHALF_(zero16, zero16, CU0, CU1, SP, BU0, BU1)
@@ -277,17 +321,30 @@ __device__ __forceinline__ void splitn(const f32x4 &xa, const f32x4 &xb, float s
 // per-pixel scale is applied when they are added to the accumulators: acc[pixel][n] += table[pixel(tap)] * tp[pixel][n] (the
 // fold table's entry, zero for the padding ring).  Step j of a (tap, image) range consumes weight unit j = (n-tile j / 4,
 // slab j % 4) and loads unit j + 6 (the ring of eight); the A fragments of a slab are read twice (once per n-tile).
+#if XNPL == 2
 #define XQHALF_(C0IN, C1IN, CU0, CU1, A0, A1, BU)                                        \
     CU0 = XMFMA(A0[1], BU[0], C0IN); CU1 = XMFMA(A1[1], BU[0], C1IN);                    \
     CU0 = XMFMA(A0[0], BU[1], CU0); CU1 = XMFMA(A1[0], BU[1], CU1);                      \
     CU0 = XMFMA(A0[0], BU[0], CU0); CU1 = XMFMA(A1[0], BU[0], CU1);
+#else
+#undef XQHALF_
+#define XQHALF_(C0IN, C1IN, CU0, CU1, A0, A1, BU)                                        \
+    CU0 = XMFMA(A0[0], BU[0], C0IN); CU1 = XMFMA(A1[0], BU[0], C1IN);
+#endif
 #define XQHALF(CU0, CU1, A0, A1, BU) XQHALF_(CU0, CU1, CU0, CU1, A0, A1, BU)
 #define XQHALFZ(CU0, CU1, A0, A1, BU) XQHALF_(zero16, zero16, CU0, CU1, A0, A1, BU)
+#if XNPL == 2
 #define XQPIPE()                                                                         \
     _Pragma("unroll") for (int g_ = 0; g_ < 2 * XNPL; ++g_) {                                                        \
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }       \
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x020, XNPL, 0);          \
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+#else                                   // two MFMAs, two LDS reads, one weight load
+#undef XQPIPE
+#define XQPIPE()                                                                         \
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);             \
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+#endif
 #define XQSTEP(HALF, AC0, AC1, AN0, AN1, NP0, NP1, BC, BN, AH)                            \
     { XLOADP(AN0, NP0, XPL1) XLOADP(AN1, NP1, XPL1) XLOADB(BN, AH)                                                    \
       HALF(tp0, tp1, AC0, AC1, BC) XQPIPE() __builtin_amdgcn_sched_barrier(0); }
@@ -311,10 +368,16 @@ __device__ __forceinline__ void splitn(const f32x4 &xa, const f32x4 &xb, float s
 // against two 16-column n-tiles = 12 MFMAs of 16 cycles and two weight units.
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 #define X16MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(xe8, (a)), __builtin_bit_cast(xe8, (b)), (c), 0, 0, 0)
+#if XNPL == 2
 #define X16HALF_(C0IN, C1IN, CU0, CU1, SP, BU0, BU1)                                     \
     CU0 = X16MFMA(SP[1], BU0[0], C0IN); CU1 = X16MFMA(SP[1], BU1[0], C1IN);              \
     CU0 = X16MFMA(SP[0], BU0[1], CU0); CU1 = X16MFMA(SP[0], BU1[1], CU1);                \
     CU0 = X16MFMA(SP[0], BU0[0], CU0); CU1 = X16MFMA(SP[0], BU1[0], CU1);
+#else
+#undef X16HALF_
+#define X16HALF_(C0IN, C1IN, CU0, CU1, SP, BU0, BU1)                                     \
+    CU0 = X16MFMA(SP[0], BU0[0], C0IN); CU1 = X16MFMA(SP[0], BU1[0], C1IN);
+#endif
 #define X16HALF(CU0, CU1, SP, BU0, BU1) X16HALF_(CU0, CU1, CU0, CU1, SP, BU0, BU1)
 #define X16HALFZ(CU0, CU1, SP, BU0, BU1) X16HALF_(zero4, zero4, CU0, CU1, SP, BU0, BU1)
 // LOADNEXT: the LDS reads this pseudo-slab carries for a later one (or nothing)
@@ -330,6 +393,7 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 // (the MFMAs lead: the first ones issue as soon as the turn starts, the loads for later slabs follow in their shadow -- one load
 // behind every MFMA measured 2-3 % faster than two bursts at the head; four slabs per turn, global loads first, alternating
 // LDS / global loads, one load per two MFMAs: no better; profiles/r03_ablation_log.txt, r04_ablation_log.txt)
+#if XNPL == 2                           /* the direct conv2 exists in the two-plane pass only */
 #define XHPIPE()                                                                         \
     __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                                                                \
     _Pragma("unroll") for (int g_ = 0; g_ < 2 * XNPL; ++g_) {                                                        \
@@ -348,6 +412,7 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
     { XLOADP(AN0, NP0, HPL) XLOADP(AN1, NP1, HPL) XLOADB(BN0, AH) XLOADB(BN1, (AH) + 1)                                \
       XHMFMAS(AC0, AC1, BC0, BC1)                                                                                     \
       XHPIPE() __builtin_amdgcn_sched_barrier(0); }
+#endif
 
 // ---- the misc block: [16] floats behind the convolution buffers (XSM_MISC) -------------------------------------------
 enum : int {
@@ -474,11 +539,13 @@ __device__ __forceinline__ void gather_zero(GatherRegs &g) {
 #define XWS_V(lvl_) (args.ws + (size_t)(lvl_) * args.n * 512)
 #define XWS_NEXTP() (args.ws + ((2 * (size_t)args.n * 512 + 31) & ~(size_t)31))
 // coordinate q of proposal slot `prop` at level lvl: the caller's proposals, or the previous level's regressed matches
+#if XNPL == 2                           // (one definition serves both passes)
 __device__ __forceinline__ float proposal_coord(const RegressArgs &args, int lvl, int prop, int q) {
     if (lvl > 0) return load_coherent(XWS_NEXTP() + (size_t)prop * 4 + q);
     if (args.is_float) return ((const float *)args.proposals)[(size_t)prop * 4 + q];
     return (float)((const long long *)args.proposals)[(size_t)prop * 4 + q];
 }
+#endif
 
 // Persistent work-groups: the launch has min(n, compute units) of them (one fits a compute unit), work-group g owns the
 // proposals g, g + G, g + 2G, ...  Per level it runs the two convolutions of each of its proposals (pooled features V[512]
@@ -623,7 +690,9 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
                     const unsigned h = pk_e(v[0] * mul, v[1] * mul);
                     unsigned char *d = smb + im * XIMG + XOFF1 + cy * XRP1 + cx * XST1 + c2 * 2;
                     *(unsigned *)d = h;
+#if XNPL == 2
                     *(unsigned *)(d + XPL1) = pk_e(v[0] * mul - pk_lo(h), v[1] * mul - pk_hi(h));
+#endif
                 }
             }
             // levels 2 and 3: 2 x (25 x 64 + 9 x 128) values
@@ -854,7 +923,6 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
             // BN1 -> H (fp32, scaled per proposal) -> LDS [pixel 64 + one row of zeros][512 ch (+16 B)] -> B^T d B of the 16
             // tiles (4 x 4 windows at stride 2 over the zero-padded 8 x 8 map) -> two fp16 planes -> the A blocks of
             // wino_gemm_kernel: [position 16][row block][K chunk 16][plane 2][row 128][4 pieces of 8 ch, XOR-swizzled].
-            constexpr int HWST = 512 * 4 + 16;
             static_assert(65 * HWST <= XSM_MISC, "H as fp32 fits the convolution buffers");
             bn1_absmax();
             if (tidv < HWST / 16) {
@@ -906,7 +974,7 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
             P2P_OPAQUE(tve);
             const int lq = tve & 63, oct = lq & 3, tile = lq >> 2, ty = tile >> 2, tx = tile & 3;
             const unsigned pl = (unsigned)(cprop - args.p0);
-            const unsigned pstride = (unsigned)args.mblocks * (16u * WINO_BLK);
+            const unsigned pstride = (unsigned)args.mblocks * (16u * XWBLK);
             const unsigned rr = (pl & 7u) * 16u + (unsigned)tile;
             const unsigned inblk = (rr * 4u + ((unsigned)oct ^ ((rr >> 2) & 3u))) * 16u;
             // LDS offset of window element (aa, bb) (outside the map: the zero row); recomputed where it is used -- a table of the 16
@@ -918,8 +986,8 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
 #pragma unroll 1
             for (int i2 = 0; i2 < 2; ++i2) {
                 const int kc = wave * 2 + i2;
-                unsigned char *ub = args.wU + (size_t)(((pl >> 3) * 16u + (unsigned)kc) * (unsigned)WINO_BLK + inblk);
-                unsigned keep[16][4];                             // first pass: {h0a, h0b, h1a, h1b} of channels 0-3
+                unsigned char *ub = args.wU + (size_t)(((pl >> 3) * 16u + (unsigned)kc) * (unsigned)XWBLK + inblk);
+                unsigned keep[16][2 * XNPL];                      // first pass: {h0a, h0b, h1a, h1b} of channels 0-3
 #pragma unroll
                 for (int hh = 0; hh < 2; ++hh) {
                     f32x4 d[4][4];
@@ -942,15 +1010,23 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
                             const f32x4 v = (jj == 0) ? tr[0] - tr[2] : (jj == 1) ? tr[1] + tr[2]
                                           : (jj == 2) ? tr[2] - tr[1] : tr[1] - tr[3];
                             const unsigned h0a = pk_e(v[0], v[1]), h0b = pk_e(v[2], v[3]);
+#if XNPL == 2
                             const unsigned h1a = pk_e(v[0] - pk_lo(h0a), v[1] - pk_hi(h0a));
                             const unsigned h1b = pk_e(v[2] - pk_lo(h0b), v[3] - pk_hi(h0b));
+#endif
                             unsigned *kp = keep[ii * 4 + jj];
                             if (hh == 0) {
+#if XNPL == 2
                                 kp[0] = h0a; kp[1] = h0b; kp[2] = h1a; kp[3] = h1b;
+#else
+                                kp[0] = h0a; kp[1] = h0b;
+#endif
                             } else {
                                 unsigned char *dst = ub + (size_t)(ii * 4 + jj) * pstride;
                                 *(uint4 *)dst = make_uint4(kp[0], kp[1], h0a, h0b);
+#if XNPL == 2
                                 *(uint4 *)(dst + WINO_BLK / 2) = make_uint4(kp[2], kp[3], h1a, h1b);
+#endif
                             }
                         }
                     }
@@ -958,6 +1034,7 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
             }
             XT(9)
         } else {
+#if XNPL == 2                           // the direct conv2 of P2P_REGRESS_FP16X2: the two-plane pass only
         // BN1 -> H: every wave writes the two planes of its 64 channels into its chunk (wave >> 1)
         {
             if (tidv < 4 * XNPL * (2 * HST / 16)) {  // the two all-zero padding rows of every plane (of every chunk)
@@ -1074,6 +1151,9 @@ __global__ __launch_bounds__(NT, 2) void regress_h2_kernel(RegressArgs args) {
                 if (half == 0) XWS_V(lvl)[(size_t)prop * 512 + n] = m;       // pooled features: the FC batch of the level reads them back
             }
         }
+#else
+        static_assert(WINO, "the single-plane pass has the conv1 launch only");
+#endif
         }
         __syncthreads();       // every wave is done with the proposal's LDS (the next gather overwrites it)
         XT(11)
@@ -1126,7 +1206,11 @@ static void split_conv1_index(int slab, int half, int j, int &ch, int &tap) {
 
 // element j of lane `lane` in both planes of the unit that starts at unit_base
 static void putn(uint16_t *d, size_t unit_base, int lane, int j, float v) {
+#if XNPL == 2
     split_fp16_planes(v, &d[(unit_base + lane) * 8 + j], &d[(unit_base + 64 + lane) * 8 + j]);
+#else
+    d[(unit_base + lane) * 8 + j] = round_fp16(v);
+#endif
 }
 
 // fp16 planes: every output channel's weights are scaled by the power of two 2^t[n] that brings the largest of them into
@@ -1211,7 +1295,11 @@ void pack_h2_weights(const float *conv1_w, const float *conv2_w, float *wx1, flo
 
 static int launch_h2(const RegressArgs &a, int n, bool wino, hipStream_t stream) {
     static DeviceOnce attr_set;
+#if XNPL == 2
     const int dev = raise_lds_limit(attr_set, {{(const void *)regress_h2_kernel<false>, (int)XSM_BYTES}, {(const void *)regress_h2_kernel<true>, (int)XSM_BYTES}});
+#else
+    const int dev = raise_lds_limit(attr_set, {{(const void *)regress_h2_kernel<true>, (int)XSM_BYTES}});
+#endif
     if (dev < 0) return dev;
     const int ncu_dev = device_cu_count(dev);
     if (ncu_dev < 0) return ncu_dev;
@@ -1222,13 +1310,26 @@ static int launch_h2(const RegressArgs &a, int n, bool wino, hipStream_t stream)
     const int ncu = ncu_dev;
 #endif
     P2P_REQUIRE(a.ws, P2P_EINVAL, "%s: the scratch buffer is missing", "regress_h2_kernel");
-    if (wino) hipLaunchKernelGGL(regress_h2_kernel<true>, dim3(std::min(n, ncu)), dim3(NT), XSM_BYTES, stream, a);
+    if (wino) hipLaunchKernelGGL(XNS(regress_h2_kernel<true>), dim3(std::min(n, ncu)), dim3(NT), XSM_BYTES, stream, a);
+#if XNPL == 2
     else hipLaunchKernelGGL(regress_h2_kernel<false>, dim3(std::min(n, ncu)), dim3(NT), XSM_BYTES, stream, a);
+#endif
     return check_launch("regress_h2_kernel");
 }
 
-int launch_regress_h2(const RegressArgs &a, int n, hipStream_t stream) { return launch_h2(a, n, false, stream); }
+#if XNPL == 2
+int launch_regress_h2(const RegressArgs &a, int n, hipStream_t stream) { return XNS(launch_h2)(a, n, false, stream); }
+#endif
 // conv1 of the proposals [a.p0, a.p1) of level a.lvl0 -> the transformed conv2 input (regress_wino.hip); n = a.p1 - a.p0
-int launch_regress_h2_conv1(const RegressArgs &a, int n, hipStream_t stream) { return launch_h2(a, n, true, stream); }
+int launch_regress_h2_conv1(const RegressArgs &a, int n, hipStream_t stream) { return XNS(launch_h2)(a, n, true, stream); }
 
+#if XNPL == 1
+}  // namespace fp16x1
+#endif
 }  // namespace p2p
+
+#if XNPL == 2                           // the single-plane pass (header): this file once more, into p2p::fp16x1
+#undef XNPL
+#define XNPL 1
+#include "regress_h2.hip"
+#endif

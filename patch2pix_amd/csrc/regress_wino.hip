@@ -31,21 +31,42 @@
 // that the fragments of the next stage's first slab are prefetched behind the second slab's MFMAs).
 // The four work-groups that share a row block (output-channel blocks 0-3) get consecutive slots on the same XCD, so U is
 // fetched from HBM once and re-read from that XCD's L2.
+//
+// Single-plane pass.  Like regress_h2.hip this file includes itself at its end with WNPL 1, into namespace p2p::fp16x1: the GEMM of
+// mode P2P_REGRESS_FP16.  U and the filters are ONE fp16 plane (the same scales), a block is [row 128][4 pieces of 16 B] = 8 KB
+// with the same XOR swizzle, a stage is one LDS-DMA piece of A and one of B per wave, the ring is 64 KB, and a product is ONE
+// MFMA.  Tiling, stage order and barriers are those of the two-plane kernel; what differs is a macro or an `#if WNPL` block.
+#ifndef WNPL
+#define WNPL 2                           // fp16 planes per operand
+#endif
 #include "regress_common.h"
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+// WNS(f): a function both passes define, called with arguments of p2p's types (argument-dependent lookup would find both)
+#undef WNS
+#if WNPL == 1
+#define WNS(f) fp16x1::f
+#else
+#define WNS(f) f
+#endif
+
 namespace p2p {
+#if WNPL == 1
+namespace fp16x1 {
+#endif
 
 typedef _Float16 we8 __attribute__((ext_vector_type(8)));
 #define WMFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(we8, (a)), __builtin_bit_cast(we8, (b)), (c), 0, 0, 0)
 
 constexpr int WNT = 512;                 // threads per work-group: 8 waves, two per SIMD
-constexpr int WSTAGE = 2 * WINO_BLK;     // A block + B block
+constexpr int WBLK = WNPL * (WINO_BLK / 2);      // a block: [plane][row 128][32 K of fp16]
+constexpr int WPIECE = WBLK / 8;         // bytes of a block one wave copies: WNPL LDS-DMA pieces of 1 KiB
+constexpr int WSTAGE = 2 * WBLK;         // A block + B block
 constexpr int WRING = 4;
-constexpr int WLDS = WRING * WSTAGE;     // 128 KB
+constexpr int WLDS = WRING * WSTAGE;     // 128 KB (one plane: 64 KB)
 static_assert(WINO_BLK == 2 * 128 * 64, "block = [plane 2][row 128][32 K of fp16]");
 
 struct WinoArgs {
@@ -63,37 +84,58 @@ struct WinoArgs {
 };
 
 // one stage = 4 LDS-DMA pieces of 1 KiB per wave: wave w copies bytes [2048 w, 2048 w + 2048) of the A and of the B block
+// (one plane: 2 pieces, bytes [1024 w, 1024 w + 1024))
+#if WNPL == 2
+#define WDMA(ga_, gb_, la_)                                                                                            \
+        P2P_GLOBAL_LOAD_LDS16(ga_ + lane16, la_, 0); P2P_GLOBAL_LOAD_LDS16(ga_ + lane16, la_, 1024);                   \
+        P2P_GLOBAL_LOAD_LDS16(gb_ + lane16, la_ + WBLK, 0); P2P_GLOBAL_LOAD_LDS16(gb_ + lane16, la_ + WBLK, 1024);
+#define WWAIT_TWO_IN_FLIGHT() P2P_WAIT_VMCNT(8)
+#define WWAIT_ONE_IN_FLIGHT() P2P_WAIT_VMCNT(4)
+#else
+#undef WDMA
+#undef WWAIT_TWO_IN_FLIGHT
+#undef WWAIT_ONE_IN_FLIGHT
+#define WDMA(ga_, gb_, la_)                                                                                            \
+        P2P_GLOBAL_LOAD_LDS16(ga_ + lane16, la_, 0); P2P_GLOBAL_LOAD_LDS16(gb_ + lane16, la_ + WBLK, 0);
+#define WWAIT_TWO_IN_FLIGHT() P2P_WAIT_VMCNT(4)
+#define WWAIT_ONE_IN_FLIGHT() P2P_WAIT_VMCNT(2)
+#endif
 #define WISSUE(ST, SLOT)                                                                                               \
     {                                                                                                                  \
         const int st_ = (ST) < 256 ? (ST) : 255;          /* past the end: reload the last stage into a free slot */  \
         const int p_ = st_ >> 4, kc_ = st_ & 15;                                                                       \
-        const unsigned char *ga_ = a.U + ((size_t)(p_ * a.mblocks + mb) * 16 + kc_) * WINO_BLK + woff;                  \
-        const unsigned char *gb_ = a.Wt + ((size_t)((p_ * 4 + nb) * 16 + kc_)) * WINO_BLK + woff;                       \
-        unsigned char *la_ = smb + (SLOT) * WSTAGE + wave * 2048;                                                      \
-        P2P_GLOBAL_LOAD_LDS16(ga_ + lane16, la_, 0); P2P_GLOBAL_LOAD_LDS16(ga_ + lane16, la_, 1024);                   \
-        P2P_GLOBAL_LOAD_LDS16(gb_ + lane16, la_ + WINO_BLK, 0); P2P_GLOBAL_LOAD_LDS16(gb_ + lane16, la_ + WINO_BLK, 1024); \
+        const unsigned char *ga_ = a.U + ((size_t)(p_ * a.mblocks + mb) * 16 + kc_) * WBLK + woff;                      \
+        const unsigned char *gb_ = a.Wt + ((size_t)((p_ * 4 + nb) * 16 + kc_)) * WBLK + woff;                           \
+        unsigned char *la_ = smb + (SLOT) * WSTAGE + wave * WPIECE;                                                    \
+        WDMA(ga_, gb_, la_)                                                                                            \
     }
 // fragments of slab S (0, 1) of ring slot SLOT: A[m-tile][plane], B[plane]
 #define WREAD(FA, FB, SLOT, S)                                                                                         \
     {                                                                                                                  \
         const unsigned char *pa_ = smb + (SLOT) * WSTAGE + ((S) ? aoff1 : aoff0);                                      \
-        const unsigned char *pb_ = smb + (SLOT) * WSTAGE + WINO_BLK + ((S) ? boff1 : boff0);                            \
-        _Pragma("unroll") for (int q_ = 0; q_ < 2; ++q_) {                                                             \
+        const unsigned char *pb_ = smb + (SLOT) * WSTAGE + WBLK + ((S) ? boff1 : boff0);                                \
+        _Pragma("unroll") for (int q_ = 0; q_ < WNPL; ++q_) {                                                           \
             FA[0][q_] = *(const f32x4 *)(pa_ + q_ * 8192);                                                             \
             FA[1][q_] = *(const f32x4 *)(pa_ + 2048 + q_ * 8192);                                                      \
             FB[q_] = *(const f32x4 *)(pb_ + q_ * 8192);                                                                \
         }                                                                                                              \
     }
-// 6 MFMAs of a slab; smallest terms first; the two accumulators alternate
+// 6 MFMAs of a slab; smallest terms first; the two accumulators alternate (one plane: 2 MFMAs)
+#if WNPL == 2
 #define WSLAB_(FA, FB, C0, C1)                                                                                         \
     M0 = WMFMA(FA[0][1], FB[0], C0); M1 = WMFMA(FA[1][1], FB[0], C1);                                                  \
     M0 = WMFMA(FA[0][0], FB[1], M0); M1 = WMFMA(FA[1][0], FB[1], M1);                                                  \
     M0 = WMFMA(FA[0][0], FB[0], M0); M1 = WMFMA(FA[1][0], FB[0], M1);
+#else
+#undef WSLAB_
+#define WSLAB_(FA, FB, C0, C1) M0 = WMFMA(FA[0][0], FB[0], C0); M1 = WMFMA(FA[1][0], FB[0], C1);
+#endif
 #define WSLAB(FA, FB) WSLAB_(FA, FB, M0, M1)
 #define WSLABZ(FA, FB) WSLAB_(FA, FB, zero16, zero16)
 
 // The compiler folds a software prefetch back into read -> wait -> MFMA chains unless the interleave is pinned: one LDS read
 // (and, in the half of a stage that issues the next DMA, LDS-DMA pieces) behind each MFMA of a slab.
+#if WNPL == 2
 #define WPIPE_A()                                                                                                      \
     _Pragma("unroll") for (int g_ = 0; g_ < 6; ++g_) {                                                                 \
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }        \
@@ -105,6 +147,20 @@ struct WinoArgs {
     _Pragma("unroll") for (int g_ = 0; g_ < 2; ++g_) {                                                                 \
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }        \
     __builtin_amdgcn_sched_barrier(0);
+#else                                    // 2 MFMAs, 3 LDS reads (and 2 LDS-DMA pieces in the second half of a stage)
+#undef WPIPE_A
+#undef WPIPE_B
+#define WPIPE_A()                                                                                                      \
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);              \
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);              \
+    __builtin_amdgcn_sched_barrier(0);
+#define WPIPE_B()                                                                                                      \
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);              \
+    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                                                 \
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);              \
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                                 \
+    __builtin_amdgcn_sched_barrier(0);
+#endif
 
 __global__ __launch_bounds__(WNT, 1) void wino_gemm_kernel(WinoArgs a) {
     P2P_DYN_SHARED(unsigned char, smb);
@@ -116,7 +172,7 @@ __global__ __launch_bounds__(WNT, 1) void wino_gemm_kernel(WinoArgs a) {
     const int nb = q & 3, mb = (q >> 2) * 8 + xcd;
     if (mb >= a.mblocks || wino_slot(a, a.p0 + mb * 8) < 0) return;      // no row block, or none of its proposals exists
     const int wm = wave >> 2, wn = wave & 3;          // this wave's tile: rows [64 wm, +64), columns [32 wn, +32)
-    const unsigned lane16 = lane * 16, woff = wave * 2048;
+    const unsigned lane16 = lane * 16, woff = wave * WPIECE;
     // fragment addresses inside a block: row r, piece (2 slab + half) ^ ((r >> 2) & 3)
     const int sw = (l31 >> 2) & 3;
     const unsigned aoff0 = ((wm * 64 + l31) * 4 + ((0 + half) ^ sw)) * 16, aoff1 = ((wm * 64 + l31) * 4 + ((2 + half) ^ sw)) * 16;
@@ -128,10 +184,10 @@ __global__ __launch_bounds__(WNT, 1) void wino_gemm_kernel(WinoArgs a) {
     for (int ab = 0; ab < 4; ++ab)
 #pragma unroll
         for (int t = 0; t < 2; ++t) Y[ab][t] = zero16;
-    f32x4 XA[2][2], XB[2], YA[2][2], YB[2];
+    f32x4 XA[2][WNPL], XB[WNPL], YA[2][WNPL], YB[WNPL];
 
     WISSUE(0, 0) WISSUE(1, 1) WISSUE(2, 2)
-    P2P_WAIT_VMCNT(8);
+    WWAIT_TWO_IN_FLIGHT();
     __builtin_amdgcn_s_barrier();
     WREAD(XA, XB, 0, 0)
     __builtin_amdgcn_sched_barrier(0);
@@ -148,7 +204,7 @@ __global__ __launch_bounds__(WNT, 1) void wino_gemm_kernel(WinoArgs a) {
             WPIPE_A()
             // stage st + 1 has landed (this wave's pieces; the barrier extends that to everybody's) and every wave is
             // past stage st - 1, whose slot stage st + 3 overwrites
-            P2P_WAIT_VMCNT(4);
+            WWAIT_ONE_IN_FLIGHT();
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
             WISSUE(p * 16 + kc + 3, (kc + 3) & 3)
@@ -205,12 +261,14 @@ __global__ __launch_bounds__(WNT) void wino_zero_tail_kernel(WinoArgs a, unsigne
         // the 16 rows of proposal j of the block: lane = (tile, piece of 8 channels), wave w the K chunks 2 w and 2 w + 1
         const unsigned rr = (unsigned)j * 16u + ((unsigned)lane >> 2);
         const unsigned inblk = (rr * 4u + (((unsigned)lane & 3u) ^ ((rr >> 2) & 3u))) * 16u;
-        const size_t pstride = (size_t)a.mblocks * (16u * WINO_BLK);
+        const size_t pstride = (size_t)a.mblocks * (16u * WBLK);
         for (int i2 = 0; i2 < 2; ++i2) {
-            unsigned char *ub = U + (size_t)(((unsigned)mb * 16u + (unsigned)(wave * 2 + i2)) * (unsigned)WINO_BLK + inblk);
+            unsigned char *ub = U + (size_t)(((unsigned)mb * 16u + (unsigned)(wave * 2 + i2)) * (unsigned)WBLK + inblk);
             for (int pos = 0; pos < 16; ++pos) {
                 *(uint4 *)(ub + pos * pstride) = make_uint4(0u, 0u, 0u, 0u);
+#if WNPL == 2
                 *(uint4 *)(ub + pos * pstride + WINO_BLK / 2) = make_uint4(0u, 0u, 0u, 0u);
+#endif
             }
         }
         if (tid == 0) hinv[mb * 8 + j] = 0.f;
@@ -219,11 +277,13 @@ __global__ __launch_bounds__(WNT) void wino_zero_tail_kernel(WinoArgs a, unsigne
 
 // FC tail of a level as its own launch (the one-launch kernel runs it at the end of a work-group's share): same work
 // distribution, same code (fc_batch_parse, regress_common.h).
+#if WNPL == 2                            // one kernel for both passes
 __global__ __launch_bounds__(NT, 2) void regress_fc_kernel(RegressArgs args, int lvl) {
     P2P_DYN_SHARED(unsigned char, smb);
     fc_batch_parse(args.reg[lvl], args, lvl, args.ws + (size_t)lvl * args.n * 512,
                    args.ws + ((2 * (size_t)args.n * 512 + 31) & ~(size_t)31), smb, threadIdx.x);
 }
+#endif
 
 // --------------------------------------------------------------------------------------------------
 // host side
@@ -254,9 +314,13 @@ void pack_wino_weights(const float *conv2_w, float *out, int *t2) {
             for (int k = 0; k < 512; ++k) {
                 const int kc = k >> 5, qq = (k >> 3) & 3, e = k & 7;
                 const float v = (float)std::ldexp(wt[((size_t)p * 512 + n) * 512 + k], t2[n]);
-                const size_t blk = ((size_t)(p * 4 + nb) * 16 + kc) * (WINO_BLK / 2);       // in fp16 elements
+                const size_t blk = ((size_t)(p * 4 + nb) * 16 + kc) * (WBLK / 2);           // in fp16 elements
                 const size_t in = (size_t)(col * 4 + (qq ^ ((col >> 2) & 3))) * 8 + e;
+#if WNPL == 2
                 split_fp16_planes(v, &d[blk + in], &d[blk + 128 * 32 + in]);
+#else
+                d[blk + in] = round_fp16(v);      // rounded once, from the fp64 transform
+#endif
             }
         }
 }
@@ -272,7 +336,7 @@ int launch_regress_wino(const RegressArgs &args, int n, hipStream_t stream) {
     const int ncu = device_cu_count(dev);
     if (ncu < 0) return ncu;
     P2P_REQUIRE(a.ws, P2P_EINVAL, "%s: the scratch buffer is missing", "launch_regress_wino");
-    unsigned char *wsU = (unsigned char *)(a.ws + wino_u_offset_floats((size_t)n));
+    unsigned char *wsU = (unsigned char *)(a.ws + wino_u_offset_floats((size_t)n));      // (the same offsets in both passes)
     float *hinv = a.ws + wino_hinv_offset_floats((size_t)n);
     for (int lvl = 0; lvl < a.nlevels; ++lvl) {
         for (int ch = 0, nch = wino_nchunks((size_t)n); ch < nch; ++ch) {
@@ -292,11 +356,11 @@ int launch_regress_wino(const RegressArgs &args, int n, hipStream_t stream) {
                 WinoArgs wz = w;
                 wz.p0 = p0 + mb0 * 8;
                 hipLaunchKernelGGL(wino_zero_tail_kernel, dim3(mblocks - mb0), dim3(WNT), 0, stream, wz,
-                                   wsU + (size_t)mb0 * 16 * WINO_BLK, hinv + mb0 * 8, p0 + cn);
+                                   wsU + (size_t)mb0 * 16 * WBLK, hinv + mb0 * 8, p0 + cn);
                 st = check_launch("wino_zero_tail_kernel");
                 if (st != P2P_OK) return st;
             }
-            st = launch_regress_h2_conv1(a, cn, stream);
+            st = WNS(launch_regress_h2_conv1)(a, cn, stream);
             if (st != P2P_OK) return st;
             hipLaunchKernelGGL(wino_gemm_kernel, dim3(((mblocks + 7) / 8) * 32), dim3(WNT), WLDS, stream, w);
             st = check_launch("wino_gemm_kernel");
@@ -309,4 +373,13 @@ int launch_regress_wino(const RegressArgs &args, int n, hipStream_t stream) {
     return P2P_OK;
 }
 
+#if WNPL == 1
+}  // namespace fp16x1
+#endif
 }  // namespace p2p
+
+#if WNPL == 2                            // the single-plane pass (header): this file once more, into p2p::fp16x1
+#undef WNPL
+#define WNPL 1
+#include "regress_wino.hip"
+#endif

@@ -399,24 +399,28 @@ class RegressorWeights:
     def set_mode(self, mode):
         """'fp16x2w' (default: fp32-equivalent, two fp16 planes under exact power-of-two scales, 3 MFMA products, the second
         convolution as Winograd F(2x2,3x3) GEMMs), 'fp16x2' (the same arithmetic, both convolutions direct, one launch) or 'f32'
-        (exact fp32 MFMA).  The first selection of a
+        (exact fp32 MFMA) -- all three fp32-equivalent -- or the opt-in 'fp16' (the structure of 'fp16x2w' with ONE fp16 plane per
+        operand and one MFMA product: relative operand rounding 2^-11, NOT held to the 1e-3 px / 1e-5 bars of the others;
+        DESIGN.md section 4, "Single-plane mode").  The first selection of a
         non-default mode packs and uploads that mode's weight stream (host work, ~1 s)."""
         if self.generic:
             if mode == "generic":
                 return
             raise NotImplementedError(f"regressor mode {mode!r}: a generic regressor runs the exact-fp32 generic kernels only")
-        if mode not in _lib.REGRESS_MODES:
+        modes = {**_lib.REGRESS_MODES, **_lib.REGRESS_MODES_LOSSY}
+        if mode not in modes:
             removed = {"bf16x2": "round 5", "bf16x3": "round 4"}
             why = f" ({mode!r} was removed in {removed[mode]})" if mode in removed else ""
-            raise ValueError(f"unknown regressor mode {mode!r}{why}: one of {sorted(_lib.REGRESS_MODES)}")
+            raise ValueError(f"unknown regressor mode {mode!r}{why}: one of {sorted(modes)}")
         # packing another mode's weight stream allocates and copies on the CURRENT device: make that the handle's device
         with torch.cuda.device(self.device):
-            _lib.check(_lib.p2p_regressor_set_mode(self.handle, _lib.REGRESS_MODES[mode]), "p2p_regressor_set_mode")
+            _lib.check(_lib.p2p_regressor_set_mode(self.handle, modes[mode]), "p2p_regressor_set_mode")
 
     @property
     def mode(self):
         code = _lib.p2p_regressor_get_mode(self.handle)
-        return "generic" if code == _lib.REGRESS_GENERIC else {v: k for k, v in _lib.REGRESS_MODES.items()}[code]
+        names = {v: k for k, v in {**_lib.REGRESS_MODES, **_lib.REGRESS_MODES_LOSSY}.items()}
+        return "generic" if code == _lib.REGRESS_GENERIC else names[code]
 
     def __del__(self):
         if getattr(self, "handle", None) and _lib is not None:
