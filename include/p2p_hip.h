@@ -14,8 +14,8 @@
  *   - all launches are asynchronous on `stream` (a hipStream_t passed as void*; NULL = default stream);
  *   - threading: every launch function is re-entrant per stream and may be called from several host threads (distinct
  *     streams, or one stream with the caller's own ordering); the weight handles are immutable after creation
- *     (p2p_regressor_set_mode / p2p_ncn_set_tile / p2p_conv_set_tile mutate a handle and must not race with launches that
- *     use it).  The only process-wide state is a per-device "kernel attributes set" flag per launcher (dynamic-LDS size via
+ *     (p2p_regressor_set_mode / p2p_ncn_set_tile / p2p_conv_set_tile / p2p_conv_set_mode / p2p_stem_set_mode mutate a
+ *     handle and must not race with launches that use it).  The only process-wide state is a per-device "kernel attributes set" flag per launcher (dynamic-LDS size via
  *     hipFuncSetAttribute, compute-unit count): atomic, set after idempotent work, so two threads meeting on a device's
  *     first launch both do that work and neither sees a half-initialised value;
  *   - dense tensors are contiguous fp32 in the layout PyTorch produces (NCHW without the N);
@@ -508,6 +508,17 @@ void p2p_conv_destroy(p2p_conv *conv);
  * [32 nt wn channels]; (0,0,0) = chosen from the launch size (default).  A tile the layer does not have is ignored.  The
  * result does not depend on the tile (every tile sums an output's K axis in the same order).                          */
 int p2p_conv_set_tile(p2p_conv *conv, int mt, int nt, int wn);
+/* The arithmetic of this handle's launches (since version 112).  P2P_CONV_FP16X2 is the default described above.
+ * P2P_CONV_FP16 is opt-in and NOT fp32-equivalent: the same kernels with ONE fp16 plane per operand (the fp16 rounding of
+ * the activation and of the weight under the same exact power-of-two scales: relative operand rounding 2^-11) and one MFMA
+ * product per fp32 product; scales, fp32 accumulation, epilogue, tiles and ymax are the default's.  Both modes read the one
+ * packed weight blob, so a mode change uploads nothing and p2p_conv_set_tile works in both.  Features computed in this mode
+ * move the correlation volume: coarse match indices can differ from the default mode's at near-ties, and the mode is not
+ * held to the index / 1e-3 px bars of the other paths.  An unknown mode is P2P_EINVAL.                              */
+#define P2P_CONV_FP16X2 0
+#define P2P_CONV_FP16   1
+int p2p_conv_set_mode(p2p_conv *conv, int mode);
+int p2p_conv_get_mode(const p2p_conv *conv);
 
 /* y = [relu](bn(conv(x)) [+ residual]) for a batch of n images.  Activations are fp32 **NHWC** device arrays
  * (x [n,h,w,ci], y and residual [n,ho,wo,co], ho = (h + 2 (ks/2) - ks) / stride + 1); xmax [n] holds the float bits of
@@ -524,6 +535,9 @@ int p2p_conv_forward(const p2p_conv *conv, const float *x, const int *xmax, int 
 typedef struct p2p_stem p2p_stem;
 int p2p_stem_create(const float *weight, const p2p_bn_params *bn, p2p_stem **out);
 void p2p_stem_destroy(p2p_stem *stem);
+/* P2P_CONV_FP16X2 (default) / P2P_CONV_FP16, as p2p_conv_set_mode (since version 112).                              */
+int p2p_stem_set_mode(p2p_stem *stem, int mode);
+int p2p_stem_get_mode(const p2p_stem *stem);
 int p2p_stem_forward(const p2p_stem *stem, const float *image, const int *imax, int n, int h, int w, float *y, p2p_stream_t stream);
 
 /* MaxPool2d(kernel 3, stride 2, padding 1) -- reference networks/resnet.py:104,146: x [n,c,h,w] NCHW -> y [n,hp,wp,c]

@@ -160,11 +160,17 @@ p2p_conv_create = _sig("p2p_conv_create", ctypes.c_int,
                        [ctypes.c_void_p, ctypes.POINTER(BnParams)] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_void_p)])
 p2p_conv_destroy = _sig("p2p_conv_destroy", None, [ctypes.c_void_p])
 p2p_conv_set_tile = _sig("p2p_conv_set_tile", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int])
+p2p_conv_set_mode = _sig("p2p_conv_set_mode", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int])
+p2p_conv_get_mode = _sig("p2p_conv_get_mode", ctypes.c_int, [ctypes.c_void_p])
+# P2P_CONV_FP16X2 (default, fp32-equivalent) / P2P_CONV_FP16 (opt-in, one fp16 plane per operand: NOT fp32-equivalent)
+BACKBONE_MODES = {"fp16x2": 0, "fp16": 1}
 p2p_conv_forward = _sig("p2p_conv_forward", ctypes.c_int,
                         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 3 +
                         [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, c_stream])
 p2p_stem_create = _sig("p2p_stem_create", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(BnParams), ctypes.POINTER(ctypes.c_void_p)])
 p2p_stem_destroy = _sig("p2p_stem_destroy", None, [ctypes.c_void_p])
+p2p_stem_set_mode = _sig("p2p_stem_set_mode", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int])
+p2p_stem_get_mode = _sig("p2p_stem_get_mode", ctypes.c_int, [ctypes.c_void_p])
 p2p_stem_forward = _sig("p2p_stem_forward", ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p, c_stream])
 p2p_maxpool_nhwc = _sig("p2p_maxpool_nhwc", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_void_p, c_stream])
 p2p_nhwc_to_nchw = _sig("p2p_nhwc_to_nchw", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p, c_stream])
@@ -205,7 +211,8 @@ EXPORTS = ["p2p_version", "p2p_last_error", "p2p_ncn_create", "p2p_ncn_destroy",
            "p2p_neigh_consensus_workspace_bytes", "p2p_resize_workspace_bytes", "p2p_resize_bicubic_batch",
            "p2p_coarse_score_workspace_bytes", "p2p_coarse_score_batch", "p2p_epipolar_batch",
            "p2p_correlation_batch", "p2p_maxpool4d_batch", "p2p_mutual_matching_workspace_bytes", "p2p_mutual_matching_batch",
-           "p2p_conv4d_create", "p2p_conv4d_destroy", "p2p_conv4d_forward_batch", "p2p_l2_normalize"]
+           "p2p_conv4d_create", "p2p_conv4d_destroy", "p2p_conv4d_forward_batch", "p2p_l2_normalize",
+           "p2p_conv_set_mode", "p2p_conv_get_mode", "p2p_stem_set_mode", "p2p_stem_get_mode"]
 
 
 def check(status, what):

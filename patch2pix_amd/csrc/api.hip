@@ -14,9 +14,9 @@ void set_error(const char *fmt, ...) {
 }  // namespace p2p
 
 #ifdef P2P_EXPERIMENT
-extern "C" int p2p_version(void) { return 111 | P2P_VERSION_EXPERIMENT; }
+extern "C" int p2p_version(void) { return 112 | P2P_VERSION_EXPERIMENT; }
 #else
-extern "C" int p2p_version(void) { return 111; }
+extern "C" int p2p_version(void) { return 112; }
 #endif
 extern "C" const char *p2p_last_error(void) { return p2p::g_err; }
 

@@ -14,6 +14,10 @@
 // v_mfma_f32_32x32x16_f16 (a0 b0 + a0 b1 + a1 b0).  Chunks are double buffered: the global loads of chunk c + 1 are in
 // flight during the MFMAs of chunk c, one barrier per chunk.  Epilogue: acc x (BN scale / weight scale / activation
 // scale) + BN shift [+ skip] [ReLU] -> fp32 NHWC (32 consecutive channels of a pixel per half wave), running max.
+//
+// P2P_CONV_FP16 (opt-in per handle, NOT fp32-equivalent): the same kernels with NP = 1 plane.  Only h0, the fp16 rounding of
+// the scaled activation, is staged (half the LDS), only plane 0 of the packed weights is read (the same rounding of the scaled
+// weight, addressed in place: nothing is packed or uploaded for the mode) and one MFMA is issued per slab and tile pair.
 #include "host_pack.h"
 
 #include <algorithm>
@@ -64,7 +68,8 @@ __device__ __forceinline__ void bb_split(const f32x4 &xa, const f32x4 &xb, float
 // MT m-tiles (32 pixels = 2 rows x 16 columns) x NT n-tiles (32 channels) per wave, WN waves along the channels (4 / WN
 // along the rows), NIT staged 8-channel pieces per thread and chunk
 // DB: slabs of weights in flight (ring of register sets; 3 for the small tiles of 3x3 convolutions, whose slabs are short)
-template <int MT, int NT, int WN, int NIT, int DB>
+// NP: fp16 planes per operand (2: a0 b0 + a0 b1 + a1 b0, the default; 1: a0 b0 alone, P2P_CONV_FP16)
+template <int MT, int NT, int WN, int NIT, int DB, int NP>
 __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
     P2P_DYN_SHARED(unsigned char, sm);
     constexpr int WM = 4 / WN, TH = 2 * MT * WM, TW = 16;
@@ -79,7 +84,7 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
     const int S = a.stride, KS = a.ks, PAD = KS >> 1;
     const int IH = (TH - 1) * S + KS, IW = (TW - 1) * S + KS;
     const int CK = a.ck, SPC = CK >> 4, gs = (CK == 32) ? 2 : 1, PS = CK * 2 + 16;
-    const int PLB = (IH * IW * PS + 15) & ~15, BUFB = 2 * PLB;
+    const int PLB = (IH * IW * PS + 15) & ~15, BUFB = NP * PLB;
     const int iy0 = oy0 * S - PAD, ix0 = ox0 * S - PAD;
     const float *xi = a.x + (size_t)img * a.h * a.w * a.ci;
 
@@ -118,7 +123,7 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
             bb_split(xr[it][0], xr[it][1], ((sok >> it) & 1u) ? up : 0.f, p0, p1);
             if ((sok >> (8 + it)) & 1u) {
                 *(f32x4 *)(dst + sdst[it]) = p0;
-                *(f32x4 *)(dst + PLB + sdst[it]) = p1;
+                if constexpr (NP == 2) *(f32x4 *)(dst + PLB + sdst[it]) = p1;
             }
         }
     };
@@ -144,13 +149,13 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     constexpr bool INPLACE = DB > 1 || MT * NT >= 8;
-    f32x4 bq[DB][NT][2];
+    f32x4 bq[DB][NT][NP];
 #pragma unroll
     for (int d = 0; d < DB; ++d)
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             bq[d][j][0] = *(const f32x4 *)(wb + d * wstep + j * 2048);
-            bq[d][j][1] = *(const f32x4 *)(wb + d * wstep + j * 2048 + 1024);
+            if constexpr (NP == 2) bq[d][j][1] = *(const f32x4 *)(wb + d * wstep + j * 2048 + 1024);
         }
     stage_load(0);
     stage_commit(0);
@@ -159,11 +164,11 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
     for (int c = 0; c < nchunks; ++c) {
         if (c + 1 < nchunks) stage_load(c + 1);
         const unsigned char *buf = sm + (c & 1) * BUFB;
-        f32x4 av[MT][2];
+        f32x4 av[MT][NP];
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             av[i][0] = *(const f32x4 *)(buf + abase[i]);
-            av[i][1] = *(const f32x4 *)(buf + PLB + abase[i]);
+            if constexpr (NP == 2) av[i][1] = *(const f32x4 *)(buf + PLB + abase[i]);
         }
         int tyy = 0, txx = 0, sl = 0;
         for (int s = 0; s < nsl; s += DB) {                   // (DB divides the slabs of a chunk: host side)
@@ -174,11 +179,11 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
                     if (++sl == SPC) { sl = 0; if (++txx == KS) { txx = 0; ++tyy; } }
                 }
                 const int naoff = (tyy * IW + txx) * PS + sl * 32;
-                f32x4 na[MT][2];
+                f32x4 na[MT][NP];
 #pragma unroll
                 for (int i = 0; i < MT; ++i) {
                     na[i][0] = *(const f32x4 *)(buf + abase[i] + naoff);
-                    na[i][1] = *(const f32x4 *)(buf + PLB + abase[i] + naoff);
+                    if constexpr (NP == 2) na[i][1] = *(const f32x4 *)(buf + PLB + abase[i] + naoff);
                 }
                 wb += wstep;                                  // (DB slabs of zeros follow the last one)
                 __builtin_amdgcn_sched_barrier(0);
@@ -189,31 +194,35 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
                     // the MFMAs by product and issue all the loads at the end of the slab.)
 #pragma unroll
                     for (int j = 0; j < NT; ++j) {
+                        if constexpr (NP == 2) {
 #pragma unroll
-                        for (int i = 0; i < MT; ++i) acc[i][j] = BB_MFMA(av[i][1], bq[d][j][0], acc[i][j]);
+                            for (int i = 0; i < MT; ++i) acc[i][j] = BB_MFMA(av[i][1], bq[d][j][0], acc[i][j]);
 #pragma unroll
-                        for (int i = 0; i < MT; ++i) acc[i][j] = BB_MFMA(av[i][0], bq[d][j][1], acc[i][j]);
+                            for (int i = 0; i < MT; ++i) acc[i][j] = BB_MFMA(av[i][0], bq[d][j][1], acc[i][j]);
+                        }
 #pragma unroll
                         for (int i = 0; i < MT; ++i) acc[i][j] = BB_MFMA(av[i][0], bq[d][j][0], acc[i][j]);
                         bq[d][j][0] = *(const f32x4 *)(wb + (DB - 1) * wstep + j * 2048);
-                        bq[d][j][1] = *(const f32x4 *)(wb + (DB - 1) * wstep + j * 2048 + 1024);
+                        if constexpr (NP == 2) bq[d][j][1] = *(const f32x4 *)(wb + (DB - 1) * wstep + j * 2048 + 1024);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 } else {
                     // the weights of the next slab are loaded into a second register set before the MFMAs of this one
-                    f32x4 nb[NT][2];
+                    f32x4 nb[NT][NP];
 #pragma unroll
                     for (int j = 0; j < NT; ++j) {
                         nb[j][0] = *(const f32x4 *)(wb + j * 2048);
-                        nb[j][1] = *(const f32x4 *)(wb + j * 2048 + 1024);
+                        if constexpr (NP == 2) nb[j][1] = *(const f32x4 *)(wb + j * 2048 + 1024);
                     }
                     __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (NP == 2) {
 #pragma unroll
-                    for (int j = 0; j < NT; ++j) {
+                        for (int j = 0; j < NT; ++j) {
 #pragma unroll
-                        for (int i = 0; i < MT; ++i) acc[i][j] = BB_MFMA(av[i][1], bq[0][j][0], acc[i][j]);
+                            for (int i = 0; i < MT; ++i) acc[i][j] = BB_MFMA(av[i][1], bq[0][j][0], acc[i][j]);
 #pragma unroll
-                        for (int i = 0; i < MT; ++i) acc[i][j] = BB_MFMA(av[i][0], bq[0][j][1], acc[i][j]);
+                            for (int i = 0; i < MT; ++i) acc[i][j] = BB_MFMA(av[i][0], bq[0][j][1], acc[i][j]);
+                        }
                     }
 #pragma unroll
                     for (int j = 0; j < NT; ++j)
@@ -221,10 +230,16 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
                         for (int i = 0; i < MT; ++i) acc[i][j] = BB_MFMA(av[i][0], bq[0][j][0], acc[i][j]);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int j = 0; j < NT; ++j) { bq[0][j][0] = nb[j][0]; bq[0][j][1] = nb[j][1]; }
+                    for (int j = 0; j < NT; ++j) {
+                        bq[0][j][0] = nb[j][0];
+                        if constexpr (NP == 2) bq[0][j][1] = nb[j][1];
+                    }
                 }
 #pragma unroll
-                for (int i = 0; i < MT; ++i) { av[i][0] = na[i][0]; av[i][1] = na[i][1]; }
+                for (int i = 0; i < MT; ++i) {
+                    av[i][0] = na[i][0];
+                    if constexpr (NP == 2) av[i][1] = na[i][1];
+                }
             }
         }
         if (c + 1 < nchunks) stage_commit((c + 1) & 1);
@@ -277,8 +292,10 @@ struct StemArgs {
 };
 constexpr int ST_TH = 8, ST_TW = 32, ST_IH = 2 * ST_TH + 5, ST_IW = 72, ST_PLB = ST_IH * ST_IW * 8;
 
+// NP: planes per operand, as in conv_kernel (the stem multiplies from the same two-plane split, so it has the same single-plane form)
+template <int NP>
 __global__ __launch_bounds__(256, 2) void stem_kernel(StemArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char xs[2 * ST_PLB];
+    __shared__ __attribute__((aligned(16))) unsigned char xs[NP * ST_PLB];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, kb5 = lane >> 5;
     const int mt = wave & 1, rg = wave >> 1;                  // channel half, row group (4 rows)
@@ -293,12 +310,12 @@ __global__ __launch_bounds__(256, 2) void stem_kernel(StemArgs a) {
     const int sx = bb_clamp(138 - xeb, -100, 100);
     const float up = __int_as_float((127 + sx) << 23), down = __int_as_float((127 - sx) << 23);
 
-    // weights of this wave's 32 channels: 14 slabs x 2 planes
-    f32x4 wv[14][2];
+    // weights of this wave's 32 channels: 14 slabs x NP planes
+    f32x4 wv[14][NP];
 #pragma unroll
     for (int sl = 0; sl < 14; ++sl)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) wv[sl][p] = *(const f32x4 *)(a.wq + (((mt * 14 + sl) * 2 + p) * 64 + lane) * 16);
+        for (int p = 0; p < NP; ++p) wv[sl][p] = *(const f32x4 *)(a.wq + (((mt * 14 + sl) * 2 + p) * 64 + lane) * 16);
 
     // the patch: rows iy0 ... iy0 + 20, columns ix0 ... ix0 + 68 (+ 3 columns of padding), three channels + a zero
     const size_t plane = (size_t)a.h * a.w;
@@ -316,7 +333,7 @@ __global__ __launch_bounds__(256, 2) void stem_kernel(StemArgs a) {
         const unsigned r01 = bb_pk(v0 * s - bb_lo(h01), v1 * s - bb_hi(h01)), r2 = bb_pk(v2 * s - bb_lo(h2), 0.f);
         if (e0 < ST_IH * ST_IW) {
             *(bu2 *)(xs + e * 8) = (bu2){h01, h2};
-            *(bu2 *)(xs + ST_PLB + e * 8) = (bu2){r01, r2};
+            if constexpr (NP == 2) *(bu2 *)(xs + ST_PLB + e * 8) = (bu2){r01, r2};
         }
     }
     __syncthreads();
@@ -335,9 +352,12 @@ __global__ __launch_bounds__(256, 2) void stem_kernel(StemArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int off = bbase + ((2 * j + ky) * ST_IW + 4 * half) * 8;
-            const f32x4 b0 = *(const f32x4 *)(xs + off), b1 = *(const f32x4 *)(xs + ST_PLB + off);
-            acc[j] = BB_MFMA(wv[sl][1], b0, acc[j]);
-            acc[j] = BB_MFMA(wv[sl][0], b1, acc[j]);
+            const f32x4 b0 = *(const f32x4 *)(xs + off);
+            if constexpr (NP == 2) {
+                const f32x4 b1 = *(const f32x4 *)(xs + ST_PLB + off);
+                acc[j] = BB_MFMA(wv[sl][1], b0, acc[j]);
+                acc[j] = BB_MFMA(wv[sl][0], b1, acc[j]);
+            }
             acc[j] = BB_MFMA(wv[sl][0], b0, acc[j]);
         }
     }
@@ -472,9 +492,25 @@ struct p2p_conv {
     const float *sc, *sh;
     int ci, co, ks, stride;
     int tile[3];             // forced (mt, nt, wn); 0 = by the launch size
+    int mode;                // P2P_CONV_FP16X2 (two planes, the default) or P2P_CONV_FP16 (plane 0 alone)
 };
 
 using namespace p2p;
+
+static bool conv_mode_known(int mode) { return mode == P2P_CONV_FP16X2 || mode == P2P_CONV_FP16; }
+
+// Both modes read the one packed weight blob (plane 0 of a fragment is addressed on its own), so a mode change uploads nothing.
+extern "C" int p2p_conv_set_mode(p2p_conv *cv, int mode) {
+    P2P_REQUIRE(cv, P2P_EINVAL, "p2p_conv_set_mode: null handle");
+    P2P_REQUIRE(conv_mode_known(mode), P2P_EINVAL, "p2p_conv_set_mode: unknown mode %d (P2P_CONV_FP16X2 or P2P_CONV_FP16)", mode);
+    cv->mode = mode;
+    return P2P_OK;
+}
+
+extern "C" int p2p_conv_get_mode(const p2p_conv *cv) {
+    P2P_REQUIRE(cv, P2P_EINVAL, "p2p_conv_get_mode: null handle");
+    return cv->mode;
+}
 
 extern "C" int p2p_conv_set_tile(p2p_conv *cv, int mt, int nt, int wn) {
     P2P_REQUIRE(cv && mt >= 0 && nt >= 0 && wn >= 0, P2P_EINVAL, "p2p_conv_set_tile: bad argument");
@@ -529,13 +565,20 @@ extern "C" int p2p_conv_create(const float *weight, const p2p_bn_params *bn, int
 
 extern "C" void p2p_conv_destroy(p2p_conv *cv) { delete cv; }
 
-template <int MT, int NT, int WN, int NIT, int DB>
-static int launch_conv(const ConvArgs &a, dim3 grid, size_t lds, hipStream_t stream) {
+template <int MT, int NT, int WN, int NIT, int DB, int NP>
+static int launch_conv_planes(const ConvArgs &a, dim3 grid, size_t lds, hipStream_t stream) {
     static DeviceOnce attr_set;
-    const int dev = raise_lds_limit(attr_set, {{(const void *)conv_kernel<MT, NT, WN, NIT, DB>, 160 * 1024}});
+    const int dev = raise_lds_limit(attr_set, {{(const void *)conv_kernel<MT, NT, WN, NIT, DB, NP>, 160 * 1024}});
     if (dev < 0) return dev;
-    hipLaunchKernelGGL((conv_kernel<MT, NT, WN, NIT, DB>), grid, dim3(256), lds, stream, a);
+    hipLaunchKernelGGL((conv_kernel<MT, NT, WN, NIT, DB, NP>), grid, dim3(256), lds, stream, a);
     return check_launch("conv_kernel");
+}
+
+// planes: 2 (P2P_CONV_FP16X2) or 1 (P2P_CONV_FP16); lds: two buffers of that many planes
+template <int MT, int NT, int WN, int NIT, int DB>
+static int launch_conv(const ConvArgs &a, dim3 grid, int planes, size_t lds, hipStream_t stream) {
+    return planes == 1 ? launch_conv_planes<MT, NT, WN, NIT, DB, 1>(a, grid, lds, stream)
+                       : launch_conv_planes<MT, NT, WN, NIT, DB, 2>(a, grid, lds, stream);
 }
 
 extern "C" int p2p_conv_forward(const p2p_conv *cv, const float *x, const int *xmax, int n, int h, int w, const float *residual,
@@ -555,20 +598,21 @@ extern "C" int p2p_conv_forward(const p2p_conv *cv, const float *x, const int *x
     const int th = 2 * c.mt * (4 / c.wn);
     a.tiles_x = ceil_div(a.wo, 16); a.tiles_y = ceil_div(a.ho, th);
     const int ih = (th - 1) * cv->stride + cv->ks, iw = 15 * cv->stride + cv->ks;
-    const size_t lds = (size_t)2 * 2 * ((ih * iw * (a.ck * 2 + 16) + 15) & ~15);
+    const int planes = cv->mode == P2P_CONV_FP16 ? 1 : 2;
+    const size_t lds = (size_t)2 * planes * ((ih * iw * (a.ck * 2 + 16) + 15) & ~15);
     P2P_REQUIRE(lds <= 160 * 1024, P2P_EUNSUPPORTED, "p2p_conv_forward: staging tile of %zu bytes", lds);
     const dim3 grid(a.tiles_x * a.tiles_y * n, cv->co / (32 * c.nt * c.wn));
     const bool deep = cv->ks == 3;          // 18 or 9 slabs per chunk: three in flight; 1x1 convolutions have 2 or 1
-    if (c.mt == 2 && c.nt == 4 && c.wn == 2 && c.nit <= 3) return launch_conv<2, 4, 2, 3, 1>(a, grid, lds, stream);
-    if (c.mt == 1 && c.nt == 4 && c.wn == 2 && c.nit <= 3) return launch_conv<1, 4, 2, 3, 1>(a, grid, lds, stream);
+    if (c.mt == 2 && c.nt == 4 && c.wn == 2 && c.nit <= 3) return launch_conv<2, 4, 2, 3, 1>(a, grid, planes, lds, stream);
+    if (c.mt == 1 && c.nt == 4 && c.wn == 2 && c.nit <= 3) return launch_conv<1, 4, 2, 3, 1>(a, grid, planes, lds, stream);
     if (c.mt == 2 && c.nt == 2 && c.wn == 2 && c.nit <= 3)
-        return deep ? launch_conv<2, 2, 2, 3, 3>(a, grid, lds, stream) : launch_conv<2, 2, 2, 3, 1>(a, grid, lds, stream);
+        return deep ? launch_conv<2, 2, 2, 3, 3>(a, grid, planes, lds, stream) : launch_conv<2, 2, 2, 3, 1>(a, grid, planes, lds, stream);
     if (c.mt == 2 && c.nt == 2 && c.wn == 2 && c.nit <= 5)
-        return deep ? launch_conv<2, 2, 2, 5, 3>(a, grid, lds, stream) : launch_conv<2, 2, 2, 5, 1>(a, grid, lds, stream);
+        return deep ? launch_conv<2, 2, 2, 5, 3>(a, grid, planes, lds, stream) : launch_conv<2, 2, 2, 5, 1>(a, grid, planes, lds, stream);
     if (c.mt == 1 && c.nt == 2 && c.wn == 2 && c.nit <= 3)
-        return deep ? launch_conv<1, 2, 2, 3, 3>(a, grid, lds, stream) : launch_conv<1, 2, 2, 3, 1>(a, grid, lds, stream);
+        return deep ? launch_conv<1, 2, 2, 3, 3>(a, grid, planes, lds, stream) : launch_conv<1, 2, 2, 3, 1>(a, grid, planes, lds, stream);
     if (c.mt == 1 && c.nt == 2 && c.wn == 1 && c.nit <= 3)
-        return deep ? launch_conv<1, 2, 1, 3, 3>(a, grid, lds, stream) : launch_conv<1, 2, 1, 3, 1>(a, grid, lds, stream);
+        return deep ? launch_conv<1, 2, 1, 3, 3>(a, grid, planes, lds, stream) : launch_conv<1, 2, 1, 3, 1>(a, grid, planes, lds, stream);
     set_error("p2p_conv_forward: no kernel instance (%d,%d,%d) with %d staged pieces per thread", c.mt, c.nt, c.wn, c.nit);
     return P2P_EUNSUPPORTED;
 }
@@ -584,7 +628,20 @@ struct p2p_stem {
     p2p::DeviceBlob blob;    // the one allocation behind the three pointers
     const unsigned char *wq;
     const float *sc, *sh;
+    int mode;                // as in p2p_conv
 };
+
+extern "C" int p2p_stem_set_mode(p2p_stem *st, int mode) {
+    P2P_REQUIRE(st, P2P_EINVAL, "p2p_stem_set_mode: null handle");
+    P2P_REQUIRE(conv_mode_known(mode), P2P_EINVAL, "p2p_stem_set_mode: unknown mode %d (P2P_CONV_FP16X2 or P2P_CONV_FP16)", mode);
+    st->mode = mode;
+    return P2P_OK;
+}
+
+extern "C" int p2p_stem_get_mode(const p2p_stem *st) {
+    P2P_REQUIRE(st, P2P_EINVAL, "p2p_stem_get_mode: null handle");
+    return st->mode;
+}
 
 extern "C" int p2p_stem_create(const float *weight, const p2p_bn_params *bn, p2p_stem **out) {
     P2P_REQUIRE(weight && bn && out, P2P_EINVAL, "p2p_stem_create: null argument");
@@ -630,7 +687,8 @@ extern "C" int p2p_stem_forward(const p2p_stem *st, const float *image, const in
     a.x = image; a.y = y; a.xmax = imax; a.wq = st->wq; a.sc = st->sc; a.sh = st->sh; a.n = n; a.h = h; a.w = w;
     a.ho = (h - 1) / 2 + 1; a.wo = (w - 1) / 2 + 1;
     a.tiles_x = ceil_div(a.wo, ST_TW); a.tiles_y = ceil_div(a.ho, ST_TH);
-    hipLaunchKernelGGL(stem_kernel, dim3(a.tiles_x * a.tiles_y * n), dim3(256), 0, stream, a);
+    if (st->mode == P2P_CONV_FP16) hipLaunchKernelGGL(stem_kernel<1>, dim3(a.tiles_x * a.tiles_y * n), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(stem_kernel<2>, dim3(a.tiles_x * a.tiles_y * n), dim3(256), 0, stream, a);
     return check_launch("stem_kernel");
 }
 

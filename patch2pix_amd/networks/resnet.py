@@ -108,7 +108,36 @@ class ResNet34(nn.Module):
                 raise NotImplementedError(f"BatchNorm eps {self.bn1.eps}: the HIP pyramid producer folds eps = 1e-5 (set P2P_BACKBONE=miopen)")
             stem = ops.Stem(self.conv1.weight, self.bn1.weight, self.bn1.bias, self.bn1.running_mean, self.bn1.running_var, device)
             self._hip_trunk_cache, self._hip_sig = (stem, trunk), sig
+            if getattr(self, "_hip_mode", None) is not None:       # the new handles start in the default mode
+                self._apply_hip_mode()
         return self._hip_trunk_cache
+
+    def _apply_hip_mode(self):
+        stem, trunk = self._hip_trunk_cache
+        stem.set_mode(self._hip_mode)
+        for blocks in trunk:
+            for layers in blocks:
+                for layer in layers:
+                    if layer is not None:
+                        layer.set_mode(self._hip_mode)
+
+    def set_mode(self, mode):
+        """Arithmetic of the HIP pyramid producer, every packed layer: 'fp16x2' (default, fp32-equivalent) or the opt-in 'fp16'
+        (one fp16 plane per operand, one MFMA product per product: NOT fp32-equivalent, see ops.ConvBN.set_mode).  The choice
+        belongs to the module: it survives the re-pack after load_state_dict / .to().  The torch path (P2P_BACKBONE=miopen,
+        train(), non-fp32 input) does not look at it.  Must not race with a forward on another stream or thread; a captured
+        graph keeps the arithmetic it was captured with."""
+        from .. import ops
+        ops.backbone_mode_id(mode)                                  # ValueError for an unknown name, before anything changes
+        self._hip_mode = mode
+        if getattr(self, "_hip_trunk_cache", None) is not None:
+            self._apply_hip_mode()
+
+    @property
+    def mode(self):
+        """The mode `set_mode` chose, or the one new handles start in (P2P_BACKBONE_MODE, else 'fp16x2')."""
+        from .. import ops
+        return getattr(self, "_hip_mode", None) or ops.default_backbone_mode()
 
     def _pyramid_hip(self, x):
         # every launch below goes to the current stream of the CURRENT device: make the input's device current (a model on

@@ -148,9 +148,39 @@ def _parse_conv_tile(text):
 FORCED_CONV_TILE = _parse_conv_tile(os.environ["P2P_CONV_TILE"]) if os.environ.get("P2P_CONV_TILE") else None
 
 
-class ConvBN:
+def backbone_mode_id(mode):
+    """'fp16x2' | 'fp16' -> P2P_CONV_FP16X2 | P2P_CONV_FP16 (include/p2p_hip.h); anything else raises ValueError."""
+    if mode not in _lib.BACKBONE_MODES:
+        raise ValueError(f"unknown backbone mode {mode!r}: one of {sorted(_lib.BACKBONE_MODES)}")
+    return _lib.BACKBONE_MODES[mode]
+
+
+def default_backbone_mode():
+    """The mode new ConvBN / Stem handles start in: P2P_BACKBONE_MODE=fp16x2|fp16 (tools; read here, not in the library)."""
+    return os.environ.get("P2P_BACKBONE_MODE") or "fp16x2"
+
+
+class _BackboneMode:
+    """set_mode / mode of the two handle kinds of the pyramid producer (`_set_mode` / `_get_mode`: the handle kind's setter
+    and getter of the C ABI)."""
+
+    def set_mode(self, mode):
+        """'fp16x2' (default: fp32-equivalent, two fp16 planes per operand under exact power-of-two scales, 3 MFMA products)
+        or the opt-in 'fp16' (the same kernel with ONE plane per operand and one MFMA product: relative operand rounding
+        2^-11, NOT fp32-equivalent; DESIGN.md section 4, "Single-plane mode of the producer").  Both read the one packed weight
+        blob: nothing is packed or uploaded."""
+        _lib.check(self._set_mode(self.handle, backbone_mode_id(mode)), self._set_mode.__name__)
+
+    @property
+    def mode(self):
+        mid = self._get_mode(self.handle)
+        return next(k for k, v in _lib.BACKBONE_MODES.items() if v == mid)
+
+
+class ConvBN(_BackboneMode):
     """Device-resident packed Conv2d(bias=False) + BatchNorm2d (eval) of the pyramid producer
     (reference networks/resnet.py:26-60); `forward` works on fp32 NHWC activations."""
+    _set_mode, _get_mode = staticmethod(_lib.p2p_conv_set_mode), staticmethod(_lib.p2p_conv_get_mode)
 
     def __init__(self, conv_weight, bn_weight, bn_bias, bn_mean, bn_var, stride, device):
         keep = [_host(t) for t in (conv_weight, bn_weight, bn_bias, bn_mean, bn_var)]
@@ -165,6 +195,8 @@ class ConvBN:
         self.ci, self.co, self.ks, self.stride = ci, co, ks, int(stride)
         self.device = torch.device(device)
         self._tile = None
+        if default_backbone_mode() != "fp16x2":
+            self.set_mode(default_backbone_mode())
 
     def __del__(self):
         if getattr(self, "handle", None) and _lib is not None:
@@ -191,8 +223,9 @@ class ConvBN:
         return y
 
 
-class Stem:
+class Stem(_BackboneMode):
     """Device-resident packed conv1 7x7/2 + bn1 (+ ReLU) of the pyramid producer (reference networks/resnet.py:101-103)."""
+    _set_mode, _get_mode = staticmethod(_lib.p2p_stem_set_mode), staticmethod(_lib.p2p_stem_get_mode)
 
     def __init__(self, conv_weight, bn_weight, bn_bias, bn_mean, bn_var, device):
         keep = [_host(t) for t in (conv_weight, bn_weight, bn_bias, bn_mean, bn_var)]
@@ -203,6 +236,8 @@ class Stem:
         with torch.cuda.device(device):
             _lib.check(_lib.p2p_stem_create(keep[0].data_ptr(), ctypes.byref(bn), ctypes.byref(self.handle)), "p2p_stem_create")
         self.device = torch.device(device)
+        if default_backbone_mode() != "fp16x2":
+            self.set_mode(default_backbone_mode())
 
     def __del__(self):
         if getattr(self, "handle", None) and _lib is not None:
