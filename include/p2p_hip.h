@@ -14,7 +14,7 @@
  *   - all launches are asynchronous on `stream` (a hipStream_t passed as void*; NULL = default stream);
  *   - threading: every launch function is re-entrant per stream and may be called from several host threads (distinct
  *     streams, or one stream with the caller's own ordering); the weight handles are immutable after creation
- *     (p2p_regressor_set_mode / p2p_ncn_set_tile / p2p_conv_set_tile / p2p_conv_set_mode / p2p_stem_set_mode mutate a
+ *     (p2p_regressor_set_mode / p2p_ncn_set_tile / p2p_ncn_set_mode / p2p_conv_set_tile / p2p_conv_set_mode / p2p_stem_set_mode mutate a
  *     handle and must not race with launches that use it).  The only process-wide state is a per-device "kernel attributes set" flag per launcher (dynamic-LDS size via
  *     hipFuncSetAttribute, compute-unit count): atomic, set after idempotent work, so two threads meeting on a device's
  *     first launch both do that work and neither sees a half-initialised value;
@@ -76,6 +76,22 @@ typedef struct p2p_ncn_config { int n_layers, kernel_size[4], channels[4], symme
 typedef struct p2p_ncn_tensors { const float *w[4], *b[4]; } p2p_ncn_tensors;
 int p2p_ncn_create_config(const p2p_ncn_config *config, const p2p_ncn_tensors *tensors, p2p_ncn **out);
 int p2p_ncn_is_generic(const p2p_ncn *ncn);      /* 1 / 0; -1 for NULL */
+
+/* The arithmetic of the matrix-core kernels of a coarse-stage call made with this handle (p2p_coarse_forward,
+ * p2p_coarse_forward_batch, p2p_neigh_consensus_batch).  P2P_COARSE_FP16X2 is the default: fp32-equivalent, two fp16 planes
+ * per operand and three MFMA products per fp32 product.  P2P_COARSE_FP16 is opt-in and NOT fp32-equivalent: the same kernels
+ * with ONE fp16 plane per operand (the normalised features, the consensus input, its weights and its hidden volume each
+ * rounded once to fp16 behind the same exact power-of-two scales: 2^-11 relative) and one MFMA product; accumulation and
+ * every epilogue stay fp32.  Winners of near-ties may move; the index / 1e-3 px bars of the default mode do not apply.
+ * Tile, strip walk and summation order are the default mode's: a result does not depend on the tile, the batch or the
+ * workspace size in either mode.  Nothing is re-packed or uploaded on a change (the packed weights hold plane 0 already).
+ * Mutual matching, match extraction, the scores and the operator entry points (p2p_correlation_batch, p2p_conv4d_*,
+ * p2p_maxpool4d_batch) are not affected.  An unknown mode -> P2P_EINVAL; a generic handle -> P2P_EUNSUPPORTED (its kernels
+ * are exact fp32); NULL -> P2P_EINVAL from the setter, -1 from the getter.                                              */
+#define P2P_COARSE_FP16X2 0
+#define P2P_COARSE_FP16   1
+int p2p_ncn_set_mode(p2p_ncn *ncn, int mode);
+int p2p_ncn_get_mode(const p2p_ncn *ncn);
 
 /* FeatRegressNet with the released configuration (conv_kers [3,3], conv_strs [2,1],
  * conv_dims [512,512], fc_dims [512,256], feat_comb 'pre', psize 16, feat_idx [0,1,2,3]) --

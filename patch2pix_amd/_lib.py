@@ -92,6 +92,10 @@ p2p_ncn_set_tile = _sig("p2p_ncn_set_tile", ctypes.c_int, [ctypes.c_void_p] + [c
 p2p_ncn_create_config = _sig("p2p_ncn_create_config", ctypes.c_int,
                              [ctypes.POINTER(NcnConfig), ctypes.POINTER(NcnTensors), ctypes.POINTER(ctypes.c_void_p)])
 p2p_ncn_is_generic = _sig("p2p_ncn_is_generic", ctypes.c_int, [ctypes.c_void_p])
+p2p_ncn_set_mode = _sig("p2p_ncn_set_mode", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int])
+p2p_ncn_get_mode = _sig("p2p_ncn_get_mode", ctypes.c_int, [ctypes.c_void_p])
+# P2P_COARSE_FP16X2 (default, fp32-equivalent) / P2P_COARSE_FP16 (opt-in, one fp16 plane per operand: NOT fp32-equivalent)
+COARSE_MODES = {"fp16x2": 0, "fp16": 1}
 p2p_regressor_create = _sig("p2p_regressor_create", ctypes.c_int,
                             [ctypes.POINTER(RegressorParams), ctypes.POINTER(ctypes.c_void_p)])
 p2p_regressor_create_config = _sig("p2p_regressor_create_config", ctypes.c_int,
@@ -212,7 +216,7 @@ EXPORTS = ["p2p_version", "p2p_last_error", "p2p_ncn_create", "p2p_ncn_destroy",
            "p2p_coarse_score_workspace_bytes", "p2p_coarse_score_batch", "p2p_epipolar_batch",
            "p2p_correlation_batch", "p2p_maxpool4d_batch", "p2p_mutual_matching_workspace_bytes", "p2p_mutual_matching_batch",
            "p2p_conv4d_create", "p2p_conv4d_destroy", "p2p_conv4d_forward_batch", "p2p_l2_normalize",
-           "p2p_conv_set_mode", "p2p_conv_get_mode", "p2p_stem_set_mode", "p2p_stem_get_mode"]
+           "p2p_conv_set_mode", "p2p_conv_get_mode", "p2p_stem_set_mode", "p2p_stem_get_mode", "p2p_ncn_set_mode", "p2p_ncn_get_mode"]
 
 
 def check(status, what):

@@ -4,7 +4,7 @@
 //
 // Data layout in HBM (A = image 1 cells, B = image 2 cells):
 //   Fn      [row block of 128 pos'][K chunk of 32 ch][plane 2][row 128][4 pieces of 8 ch] fp16: L2-normalised layer-3
-//                         features x 2^12 as two fp16 planes, in the 16 KB blocks the correlation GEMM copies into LDS by
+//                         features x 2^12 as two fp16 planes (one plane in mode P2P_COARSE_FP16: blocks of half the size), in the 16 KB blocks the correlation GEMM copies into LDS by
 //                         LDS-DMA (piece q of row r at slot q ^ ((r >> 2) & 3): conflict-free fragment reads); positions
 //                         re-ordered cell-major so that the k^2 positions of one pooling cell are adjacent:
 //                         pos' = cell*k^2 + (i%k)*k + (j%k)  (k = 4: image A's rows permuted once more inside blocks of
@@ -53,7 +53,9 @@ constexpr float CORR_FP16_SCALE = 4096.0f;
 // the rows whose products one half e of a wave holds in its 32x32 accumulator block, in register order (corr_pool_kernel<4>).
 __device__ __forceinline__ int prep_row_k4(int pp) { return (pp & ~31) + (pp & 3) + 2 * (pp & 12) + ((pp >> 2) & 4); }
 // (PERM_A = the k = 4 instantiation: a template parameter, so that the kernel of k = 1, 2 is the code it was without it)
-template <bool PERM_A>
+// NP = planes per operand: 2 = the fp32-equivalent split (default), 1 = the single-plane mode P2P_COARSE_FP16 -- the first plane
+// alone (one rounding to fp16, 2^-11 relative), in blocks of half the size: [row 128][4 pieces of 8 ch] = 8 KB per K chunk.
+template <bool PERM_A, int NP = 2>
 __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     const int img = blockIdx.y;
     if (img == 0) {
@@ -69,11 +71,11 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     // memory (its stores are masked, so their products were never used -- but NaN bit patterns went through the matrix cores).
     // The work-group of the last positions writes them: <= 127 rows x C channels x 2 planes, 16 bytes per store.
     if (((int)blockIdx.x + 1) * PREP_P >= h * w) {
-        const int pad0 = h * w, pad1 = (pad0 + 127) & ~127, pieces = (C >> 5) * 2 * 4;      // 16-byte pieces per row
+        const int pad0 = h * w, pad1 = (pad0 + 127) & ~127, pieces = (C >> 5) * NP * 4;      // 16-byte pieces per row
         for (int e = threadIdx.x; e < (pad1 - pad0) * pieces; e += 256) {
             const int pr = pad0 + e / pieces;
-            const int r = (perm ? prep_row_k4(pr) : pr) & 127, q = e % pieces, kc = q >> 3, pl = (q >> 2) & 1, piece = q & 3;
-            unsigned short *d = Fn + ((size_t)(pad0 >> 7) * (C >> 5) + kc) * (2 * 128 * 32) + pl * (128 * 32) + (r * 4 + piece) * 8;
+            const int r = (perm ? prep_row_k4(pr) : pr) & 127, q = e % pieces, kc = q / (NP * 4), pl = (q >> 2) & (NP - 1), piece = q & 3;
+            unsigned short *d = Fn + ((size_t)(pad0 >> 7) * (C >> 5) + kc) * (NP * 128 * 32) + pl * (128 * 32) + (r * 4 + piece) * 8;
             *(f32x4 *)d = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
     }
@@ -120,19 +122,20 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
             const float x = tile[c * (PREP_P + 1) + p] * inv[p] * CORR_FP16_SCALE;
             // block (pp / 128, c / 32): [plane][row pp % 128][piece (c / 8) % 4 at slot piece ^ ((row / 4) % 4)][c % 8]
             const int r = pp & 127;
-            unsigned short *d = Fn + ((size_t)(pp >> 7) * (C >> 5) + (c >> 5)) * (2 * 128 * 32) +
+            unsigned short *d = Fn + ((size_t)(pp >> 7) * (C >> 5) + (c >> 5)) * (NP * 128 * 32) +
                                 (r * 4 + (((c >> 3) & 3) ^ ((r >> 2) & 3))) * 8 + (c & 7);
             const _Float16 h0 = (_Float16)x;
             d[0] = __builtin_bit_cast(unsigned short, h0);
-            d[128 * 32] = __builtin_bit_cast(unsigned short, (_Float16)(x - (float)h0));
+            if constexpr (NP == 2) d[128 * 32] = __builtin_bit_cast(unsigned short, (_Float16)(x - (float)h0));
         }
     }
 }
 
-void launch_prep(const PrepArgs &a, unsigned nz, hipStream_t stream) {
+void launch_prep(const PrepArgs &a, int planes, unsigned nz, hipStream_t stream) {
     const int gp = std::max(ceil_div(std::max(a.h[0] * a.w[0], a.h[1] * a.w[1]), PREP_P), ceil_div(a.nkeys + 1, 256));
-    if (a.k == 4) hipLaunchKernelGGL(prep_kernel<true>, dim3(gp, 2, nz), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(prep_kernel<false>, dim3(gp, 2, nz), dim3(256), 0, stream, a);
+    const auto kernel = planes == 1 ? (a.k == 4 ? prep_kernel<true, 1> : prep_kernel<false, 1>)
+                                    : (a.k == 4 ? prep_kernel<true, 2> : prep_kernel<false, 2>);
+    hipLaunchKernelGGL(kernel, dim3(gp, 2, nz), dim3(256), 0, stream, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -159,21 +162,23 @@ constexpr int CX_AB = 16;    // tile rows per L2-resident block of A panels (16 
                              // 960x1280: 16 rows fetch 224 MB per pair, 24 rows 246 MB, 28 rows 682 MB -- the streaming B
                              // panels and the output need the other half)
 typedef _Float16 cf16x8 __attribute__((ext_vector_type(8)));
-constexpr int CX_BLK = 2 * CT * 64;          // one operand block of a stage: [plane 2][row 128][32 K fp16] = 16 KB
-constexpr int CX_STAGE = 2 * CX_BLK, CX_LDS = 2 * CX_STAGE;
+// Sizes per plane count NP (corr_pool_kernel defines CX_BLK = cx_blk(NP), CX_STAGE = 2 CX_BLK for the macros below)
+constexpr int cx_blk(int np) { return np * CT * 64; }       // one operand block of a stage: [plane NP][row 128][32 K fp16] = 16 KB (NP = 2)
+constexpr int cx_lds(int np) { return 4 * cx_blk(np); }     // [stage 2][A|B] blocks
 __device__ __forceinline__ f32x16 cx_mfma(const f32x4 &a, const f32x4 &b, const f32x16 &c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cf16x8, a), __builtin_bit_cast(cf16x8, b), c, 0, 0, 0);
 }
-// stage IT of the tile -> ring slot SLOT: wave w copies bytes [4096 w, 4096 w + 4096) of the A and of the B block
+// stage IT of the tile -> ring slot SLOT: wave w copies bytes [CX_BLK / 4 w, CX_BLK / 4 (w + 1)) of the A and of the B block
+// (4096 bytes = four copies per block with two planes, 2048 = two with one)
 #define CX_ISSUE(IT, SLOT)                                                                                             \
     {                                                                                                                  \
         const unsigned char *ga_ = Ab + (size_t)(IT) * CX_BLK + lane16;                                                \
         const unsigned char *gb_ = Bb + (size_t)(IT) * CX_BLK + lane16;                                                \
-        unsigned char *la_ = cx + (SLOT) * CX_STAGE + wave * 4096;                                                     \
+        unsigned char *la_ = cx + (SLOT) * CX_STAGE + wave * (CX_BLK / 4);                                             \
         P2P_GLOBAL_LOAD_LDS16(ga_, la_, 0); P2P_GLOBAL_LOAD_LDS16(ga_, la_, 1024);                                     \
-        P2P_GLOBAL_LOAD_LDS16(ga_, la_, 2048); P2P_GLOBAL_LOAD_LDS16(ga_, la_, 3072);                                  \
+        if constexpr (NP == 2) { P2P_GLOBAL_LOAD_LDS16(ga_, la_, 2048); P2P_GLOBAL_LOAD_LDS16(ga_, la_, 3072); }       \
         P2P_GLOBAL_LOAD_LDS16(gb_, la_ + CX_BLK, 0); P2P_GLOBAL_LOAD_LDS16(gb_, la_ + CX_BLK, 1024);                   \
-        P2P_GLOBAL_LOAD_LDS16(gb_, la_ + CX_BLK, 2048); P2P_GLOBAL_LOAD_LDS16(gb_, la_ + CX_BLK, 3072);                \
+        if constexpr (NP == 2) { P2P_GLOBAL_LOAD_LDS16(gb_, la_ + CX_BLK, 2048); P2P_GLOBAL_LOAD_LDS16(gb_, la_ + CX_BLK, 3072); } \
     }
 // fragments of slab S of ring slot SLOT: a[m-tile][plane], b[n-tile][plane]
 #define CX_READ(FA, FB, SLOT, S)                                                                                       \
@@ -181,25 +186,27 @@ __device__ __forceinline__ f32x16 cx_mfma(const f32x4 &a, const f32x4 &b, const 
         const unsigned char *pa_ = cx + (SLOT) * CX_STAGE + ((S) ? aoff1 : aoff0);                                     \
         const unsigned char *pb_ = cx + (SLOT) * CX_STAGE + CX_BLK + ((S) ? boff1 : boff0);                            \
         _Pragma("unroll") for (int t_ = 0; t_ < 2; ++t_)                                                               \
-            _Pragma("unroll") for (int q_ = 0; q_ < 2; ++q_) {                                                         \
+            _Pragma("unroll") for (int q_ = 0; q_ < NP; ++q_) {                                                        \
                 FA[t_][q_] = *(const f32x4 *)(pa_ + t_ * 2048 + q_ * 8192);                                            \
                 FB[t_][q_] = *(const f32x4 *)(pb_ + t_ * 2048 + q_ * 8192);                                            \
             }                                                                                                          \
     }
-// smallest terms first (a1 b0, a0 b1, a0 b0); the four accumulators rotate
+// smallest terms first (a1 b0, a0 b1, a0 b0); the four accumulators rotate.  One plane: a0 b0 alone
 #define CX_SLAB(FA, FB)                                                                                                \
-    _Pragma("unroll") for (int t_ = 0; t_ < 3; ++t_) {                                                                 \
+    _Pragma("unroll") for (int t_ = (NP == 2 ? 0 : 2); t_ < 3; ++t_) {                                                 \
         const int pa_ = (t_ == 0) ? 1 : 0, pb_ = (t_ == 1) ? 1 : 0;                                                    \
         _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_)                                                               \
             _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_) acc[i_][j_] = cx_mfma(FA[i_][pa_], FB[j_][pb_], acc[i_][j_]); \
     }
-// one LDS read behind each of the first eight MFMAs of a slab (left alone the compiler builds read -> wait -> MFMA chains)
+// one LDS read behind each of the first eight MFMAs of a slab (left alone the compiler builds read -> wait -> MFMA chains);
+// one plane: a slab is four MFMAs and the next slab's four reads
 #define CX_PIPE()                                                                                                      \
-    _Pragma("unroll") for (int g_ = 0; g_ < 8; ++g_) {                                                                 \
+    _Pragma("unroll") for (int g_ = 0; g_ < 4 * NP; ++g_) {                                                            \
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }        \
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0); __builtin_amdgcn_sched_barrier(0);
+    if constexpr (NP == 2) __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                          \
+    __builtin_amdgcn_sched_barrier(0);
 
-template <int KS>
+template <int KS, int NP = 2>
 __global__ __launch_bounds__(256, 2) void corr_pool_kernel(const unsigned short *__restrict__ A, const unsigned short *__restrict__ B,
                                                            int nA, int nB, int C, float *__restrict__ P,
                                                            uint8_t *__restrict__ delta, size_t sAB, size_t sP, size_t sDelta,
@@ -207,6 +214,7 @@ __global__ __launch_bounds__(256, 2) void corr_pool_kernel(const unsigned short 
     // Persistent work-groups: XCD x = blockIdx.x % 8 owns the tiles [x * per_xcd, (x + 1) * per_xcd) of the order described
     // under "Tile order", its work-group j = blockIdx.x / 8 walks j, j + G, j + 2G, ... of them (G work-groups per XCD);
     // stage 0 of the next tile is in flight during the pooling epilogue of the current one.
+    constexpr int CX_BLK = cx_blk(NP), CX_STAGE = 2 * CX_BLK;
     const int Gx = gridDim.x >> 3, xcd = blockIdx.x & 7;
     int tj = blockIdx.x >> 3;
     // tile number -> (pair, A tile row, B tile column)
@@ -232,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void corr_pool_kernel(const unsigned short 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1;
     const int half = lane >> 5, l31 = lane & 31;
-    const unsigned lane16 = wave * 4096 + lane * 16;
+    const unsigned lane16 = wave * (CX_BLK / 4) + lane * 16;
     // fragment addresses inside a block: row r, piece (2 slab + half) ^ ((r >> 2) & 3)
     const int sw = (l31 >> 2) & 3;
     const unsigned aoff0 = ((wr * 64 + l31) * 4 + ((0 + half) ^ sw)) * 16, aoff1 = ((wr * 64 + l31) * 4 + ((2 + half) ^ sw)) * 16;
@@ -248,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void corr_pool_kernel(const unsigned short 
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = (f32x16){0};
 
-    f32x4 xa[2][2], xb[2][2], ya[2][2], yb[2][2];
+    f32x4 xa[2][NP], xb[2][NP], ya[2][NP], yb[2][NP];
 #pragma unroll 1
     for (int it = 0; it < nk; it += 2) {
         // even stage (slot 0): its pieces have landed for everybody behind the barrier, and everybody is done with slot 1
@@ -415,11 +423,12 @@ __global__ __launch_bounds__(256, 2) void corr_pool_kernel(const unsigned short 
   }
 }
 
-int launch_corr_pool(const unsigned short *fnA, const unsigned short *fnB, int nA, int nB, int C, int ksize, float *P, uint8_t *delta,
-                     size_t sAB, size_t sP, size_t sDelta, unsigned nz, hipStream_t stream) {
+int launch_corr_pool(const unsigned short *fnA, const unsigned short *fnB, int nA, int nB, int C, int ksize, int planes, float *P,
+                     uint8_t *delta, size_t sAB, size_t sP, size_t sDelta, unsigned nz, hipStream_t stream) {
     static DeviceOnce attr_set_dev;      // per device: a process may drive several GPUs
-    const int dev = raise_lds_limit(attr_set_dev, {{(const void *)corr_pool_kernel<1>, CX_LDS}, {(const void *)corr_pool_kernel<2>, CX_LDS},
-                                                   {(const void *)corr_pool_kernel<4>, CX_LDS}});
+    const int dev = raise_lds_limit(attr_set_dev, {{(const void *)corr_pool_kernel<1, 2>, cx_lds(2)}, {(const void *)corr_pool_kernel<2, 2>, cx_lds(2)},
+                                                   {(const void *)corr_pool_kernel<4, 2>, cx_lds(2)}, {(const void *)corr_pool_kernel<1, 1>, cx_lds(1)},
+                                                   {(const void *)corr_pool_kernel<2, 1>, cx_lds(1)}, {(const void *)corr_pool_kernel<4, 1>, cx_lds(1)}});
     if (dev < 0) return dev;
     const int gx = ceil_div(nB, CT), gy = ceil_div(nA, CT);
     const long long ntiles = (long long)gx * gy * nz;
@@ -428,8 +437,9 @@ int launch_corr_pool(const unsigned short *fnA, const unsigned short *fnB, int n
     const int per_xcd = (int)((ntiles + 7) / 8);
     const dim3 cgrid((unsigned)(8 * std::min(per_xcd, 64)));
     if (ksize == 1) delta = nullptr, sDelta = 0;       // nothing was pooled: no argmax to record
-    const auto kernel = ksize == 1 ? corr_pool_kernel<1> : (ksize == 4 ? corr_pool_kernel<4> : corr_pool_kernel<2>);
-    hipLaunchKernelGGL(kernel, cgrid, dim3(256), CX_LDS, stream, fnA, fnB, nA, nB, C, P, delta, sAB, sP, sDelta, gx, gy, (int)ntiles, per_xcd);
+    const auto kernel = planes == 1 ? (ksize == 1 ? corr_pool_kernel<1, 1> : (ksize == 4 ? corr_pool_kernel<4, 1> : corr_pool_kernel<2, 1>))
+                                    : (ksize == 1 ? corr_pool_kernel<1, 2> : (ksize == 4 ? corr_pool_kernel<4, 2> : corr_pool_kernel<2, 2>));
+    hipLaunchKernelGGL(kernel, cgrid, dim3(256), cx_lds(planes), stream, fnA, fnB, nA, nB, C, P, delta, sAB, sP, sDelta, gx, gy, (int)ntiles, per_xcd);
     return P2P_OK;
 }
 

@@ -63,6 +63,19 @@ extern "C" int p2p_ncn_set_tile(p2p_ncn *ncn, int ta, int tb, int tc) {
     return P2P_OK;
 }
 
+extern "C" int p2p_ncn_set_mode(p2p_ncn *ncn, int mode) {
+    P2P_REQUIRE(ncn, P2P_EINVAL, "p2p_ncn_set_mode: null handle");
+    P2P_REQUIRE(mode == P2P_COARSE_FP16X2 || mode == P2P_COARSE_FP16, P2P_EINVAL, "p2p_ncn_set_mode: unknown mode %d", mode);
+    P2P_REQUIRE(!ncn->gen, P2P_EUNSUPPORTED, "p2p_ncn_set_mode: a generic consensus handle runs exact fp32 kernels and has no modes");
+    ncn->mode = mode;
+    return P2P_OK;
+}
+
+extern "C" int p2p_ncn_get_mode(const p2p_ncn *ncn) { return ncn ? ncn->mode : -1; }
+
+// fp16 planes per operand of the handle's mode
+static int coarse_planes(const p2p_ncn *ncn) { return ncn->mode == P2P_COARSE_FP16 ? 1 : 2; }
+
 extern "C" void p2p_ncn_destroy(p2p_ncn *ncn) { delete ncn; }
 
 extern "C" size_t p2p_coarse_workspace_bytes(int channels, int hA, int wA, int hB, int wB, int ksize) {
@@ -106,6 +119,7 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
     const size_t sWs = ws.total / 4;        // every workspace buffer of pair z sits z * ws.total bytes further on
     const int per_launch = (int)std::min<size_t>(batch, workspace_bytes / ws.total);   // pairs the workspace holds at once
     const int d0 = hA / ksize, d1 = wA / ksize, d2 = hB / ksize, d3 = wB / ksize;
+    const int planes = coarse_planes(ncn);      // one plane: the feature blocks fill the first half of their (two-plane sized) buffers
     for (int z0 = 0; z0 < batch; z0 += per_launch) {
         const unsigned nz = (unsigned)std::min(per_launch, batch - z0);
         const float *fA = featA + (size_t)z0 * C * nA, *fB = featB + (size_t)z0 * C * nB;
@@ -118,8 +132,8 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
         const int nkeys = 2 * (nAc + nBc);
         int *xmax = rkey1 + nkeys;
         launch_prep(PrepArgs{{fA, fB}, {fnA, fnB}, {hA, hB}, {wA, wB}, {(size_t)C * nA, (size_t)C * nB}, C, ksize, 2 * sWs, rkey1, nkeys, sWs},
-                    nz, stream);
-        int st = launch_corr_pool(fnA, fnB, nA, nB, C, ksize, P, dout, 2 * sWs, sWs, nel, nz, stream);
+                    planes, nz, stream);
+        int st = launch_corr_pool(fnA, fnB, nA, nB, C, ksize, planes, P, dout, 2 * sWs, sWs, nel, nz, stream);
         if (st != P2P_OK) return st;
         launch_maxima(P, nAc, nBc, rkey1, ckey1, sWs, sWs, nullptr, nz, stream);
         // first mutual matching, in place on the pooled volume (+ max |X| for the consensus kernel's operand scale)
@@ -128,7 +142,7 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
             st = launch_nc_generic(*ncn->gen, P, sWs, Y, sWs, (float *)(base + ws.act), sWs, (int)nz, d0, d1, d2, d3, stream);
             Y2 = nullptr;
         } else {   // both consensus layers, both branches: relu(.) of the direct branch into Y, of the transposed one into Y2
-            st = launch_nc_fused(P, Y, Y2, sWs, (int)nz, d0, d1, d2, d3, ncn->wfused.dev<unsigned char>(), ncn->b2, xmax, sWs, ncn->tile, stream);
+            st = launch_nc_fused(P, Y, Y2, sWs, (int)nz, d0, d1, d2, d3, ncn->wfused.dev<unsigned char>(), ncn->b2, xmax, sWs, ncn->tile, planes, stream);
         }
         if (st != P2P_OK) return st;
         launch_maxima(Y, nAc, nBc, rkey2, ckey2, sWs, sWs, Y2, nz, stream);
@@ -169,7 +183,7 @@ extern "C" int p2p_neigh_consensus_batch(const float *x, int batch, int hA, int 
     P2P_HIP_CHECK(hipMemsetAsync(xmax, 0, (size_t)batch * sizeof(int), stream));
     const int st = launch_absmax(x, nel, nel, batch, xmax, 1, stream);
     if (st != P2P_OK) return st;
-    return launch_nc_fused(x, y_out, nullptr, nel, batch, hA, wA, hB, wB, ncn->wfused.dev<unsigned char>(), ncn->b2, xmax, 1, ncn->tile, stream);
+    return launch_nc_fused(x, y_out, nullptr, nel, batch, hA, wA, hB, wB, ncn->wfused.dev<unsigned char>(), ncn->b2, xmax, 1, ncn->tile, coarse_planes(ncn), stream);
 }
 
 extern "C" int p2p_delta_unpack(const uint8_t *delta, size_t n, int ksize, int64_t *out, p2p_stream_t stream) {

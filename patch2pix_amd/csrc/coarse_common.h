@@ -21,10 +21,11 @@ struct PrepArgs {
     int nkeys;
     size_t sKeys;
 };
-void launch_prep(const PrepArgs &a, unsigned nz, hipStream_t stream);
+// planes: fp16 planes per operand, 2 (P2P_COARSE_FP16X2) or 1 (P2P_COARSE_FP16) -- the same for the three matrix-core launchers
+void launch_prep(const PrepArgs &a, int planes, unsigned nz, hipStream_t stream);
 // delta: the argmax codes (ksize > 1; optional); sAB / sP / sDelta: per-pair strides of the feature planes, of P and of delta
-int launch_corr_pool(const unsigned short *fnA, const unsigned short *fnB, int nA, int nB, int C, int ksize, float *P, uint8_t *delta,
-                     size_t sAB, size_t sP, size_t sDelta, unsigned nz, hipStream_t stream);
+int launch_corr_pool(const unsigned short *fnA, const unsigned short *fnB, int nA, int nB, int C, int ksize, int planes, float *P,
+                     uint8_t *delta, size_t sAB, size_t sP, size_t sDelta, unsigned nz, hipStream_t stream);
 void launch_maxima(const float *X, int nA, int nB, int *rkey, int *ckey, size_t sX, size_t sKeys, const float *X2, unsigned nz, hipStream_t stream);
 void launch_mm_apply(const float *X, int nA, int nB, const int *rkey, const int *ckey, float *out, size_t sX, size_t sKeys,
                      size_t sOut, int *amax, const float *X2, size_t nz, hipStream_t stream);
@@ -55,7 +56,7 @@ void launch_score(const ScoreArgs &a, int batch, int normalize, hipStream_t stre
 // ---- consensus.hip: the fused kernel of the released stack --------------------------------------------------------------
 void pack_nc_fused(const float *w1, const float *b1, const float *w2, DeviceBlob &out);      // lays out and fills the staging copy
 int launch_nc_fused(const float *X, float *Y, float *Y2, size_t stride, int pairs, int d0, int d1, int d2, int d3,
-                    const unsigned char *w_dev, float b2, const int *xmax, size_t xmax_stride, const int *forced_tile,
+                    const unsigned char *w_dev, float b2, const int *xmax, size_t xmax_stride, const int *forced_tile, int planes,
                     hipStream_t stream);
 int launch_absmax(const float *x, size_t n, size_t stride, int pairs, int *out, size_t out_stride, hipStream_t stream);
 
@@ -101,6 +102,7 @@ struct p2p_ncn {
     p2p::DeviceBlob wfused;  // both layers, both branches as fp16x2 MFMA fragments (consensus.hip)
     int tile[3];             // forced (ta, tb, tc) of the fused kernel, 0 = automatic (p2p_ncn_set_tile: tests and sweeps)
     p2p::NcGen *gen;         // a generic handle (p2p_ncn_create_config): its layers; the fields above are unused then
+    int mode = 0;            // P2P_COARSE_FP16X2 / P2P_COARSE_FP16 (p2p_ncn_set_mode): planes per operand of the matrix-core kernels
     ~p2p_ncn() { p2p::nc_generic_destroy(gen); }
 };
 

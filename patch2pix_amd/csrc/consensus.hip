@@ -119,7 +119,10 @@ __host__ __device__ __forceinline__ int nc_xplane(int tc, int P) { return (9 * (
 // compile-time constants -- strides, divisions and the LDS carve-up fold away (the generic body spends more instructions on
 // scalar bookkeeping than on the matrix pipe: ~2100 per strip and wave for 72 MFMAs); FTB = 0: any other shape runs the
 // same body with the runtime values.  One work-group per compute unit (FTB = 10: all 160 KB of its LDS), two waves per SIMD.
-template <int FTB>
+// NP = planes per operand: 2 = the fp32-equivalent split; 1 = the single-plane mode P2P_COARSE_FP16 -- the first plane of X, of
+// the weight fragments (read in place from the two-plane packing) and of the hidden volume, one MFMA per product.  The LDS
+// carve-up is the one of NP = 2 (the second planes are never written or read): same tile, same strip walk.
+template <int FTB, int NP = 2>
 __global__ __launch_bounds__(NCF_THREADS, 1) void nc_fused_kernel(NcFusedArgs a) {
     P2P_DYN_SHARED(unsigned char, sm);
     constexpr bool FIXED = FTB > 0;
@@ -152,28 +155,28 @@ __global__ __launch_bounds__(NCF_THREADS, 1) void nc_fused_kernel(NcFusedArgs a)
 
     // weights of this branch -> registers (layer 1: the A operands of its MFMAs)
     const unsigned char *wb = a.w + (size_t)br * NCF_BRANCH_BYTES;
-    nf4 w1[7][2];
+    nf4 w1[7][NP];
 #pragma unroll
     for (int s = 0; s < 7; ++s)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) w1[s][p] = *(const nf4 *)(wb + ((s * 2 + p) * 64 + lane) * 16);
+        for (int p = 0; p < NP; ++p) w1[s][p] = *(const nf4 *)(wb + ((s * 2 + p) * 64 + lane) * 16);
     // ... and so do the 10 layer-2 B fragments (two waves per SIMD leave a wave 256 registers; re-reading them from LDS for
     // every pair of m-tiles was a third of layer 2's ds_read_b128 traffic)
-    nf4 w2[5][2];
+    nf4 w2[5][NP];
 #pragma unroll
     for (int s = 0; s < 5; ++s)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) w2[s][p] = *(const nf4 *)(wb + NCF_W1_BYTES + ((s * 2 + p) * 64 + lane) * 16);
+        for (int p = 0; p < NP; ++p) w2[s][p] = *(const nf4 *)(wb + NCF_W1_BYTES + ((s * 2 + p) * 64 + lane) * 16);
     // (made opaque so that their loads are waited for HERE: a wait inside the strip loop would also drain the input rows
     // prefetched for the next strip)
 #pragma unroll
     for (int s = 0; s < 7; ++s)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) P2P_OPAQUE_V4(w1[s][p]);
+        for (int p = 0; p < NP; ++p) P2P_OPAQUE_V4(w1[s][p]);
 #pragma unroll
     for (int s = 0; s < 5; ++s)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) P2P_OPAQUE_V4(w2[s][p]);
+        for (int p = 0; p < NP; ++p) P2P_OPAQUE_V4(w2[s][p]);
     const float *cf = (const float *)(wb + NCF_W1_BYTES + NCF_W2_BYTES);
     // The fp16 planes are laid out for |X| <= 1 (what MutualMatching makes of non-negative correlations).  A volume with
     // larger values (negative correlations can do that) is scaled down by the power of two 2^E that brings its largest
@@ -302,7 +305,7 @@ __global__ __launch_bounds__(NCF_THREADS, 1) void nc_fused_kernel(NcFusedArgs a)
             const float x0 = q0v[k] * m0v[k] * f, x1 = q1v[k] * m1v[k] * f;
             const unsigned h = npk(x0, x1);
             *(unsigned *)(Xs + dst) = h;
-            *(unsigned *)(Xs + XPLANE + dst) = npk(x0 - npk_lo(h), x1 - npk_hi(h));
+            if constexpr (NP == 2) *(unsigned *)(Xs + XPLANE + dst) = npk(x0 - npk_lo(h), x1 - npk_hi(h));
         }
     };
 
@@ -386,8 +389,8 @@ __global__ __launch_bounds__(NCF_THREADS, 1) void nc_fused_kernel(NcFusedArgs a)
             // the X fragments of slab sl + 1 are read while the six MFMAs of slab sl issue; sched_barrier pins that order (left to
             // itself the compiler re-uses one set of fragment registers and waits for every read right in front of its MFMA:
             // ~4000 of a strip's ~5800 layer-1 cycles were LDS latency)
-            nf4 xv[2][2][2];                                   // [buffer][tile][plane]
-            auto frags = [&](int sl, nf4 (&d)[2][2]) {
+            nf4 xv[2][2][NP];                                  // [buffer][tile][plane]
+            auto frags = [&](int sl, nf4 (&d)[2][NP]) {
                 // the lane's two tap groups of this slab: g = 4 * sl + 2 * kb + {0, 1}; group 27 does not exist (zero weights)
                 // (the four offsets are made opaque scalars: otherwise the select over the lane half becomes a lane-indexed lookup
                 // in a private array = scratch memory)
@@ -397,7 +400,7 @@ __global__ __launch_bounds__(NCF_THREADS, 1) void nc_fused_kernel(NcFusedArgs a)
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
-                    for (int p = 0; p < 2; ++p) {
+                    for (int p = 0; p < NP; ++p) {
                         const unsigned *x0 = (const unsigned *)(s2x[u] + p * XPLANE + o0 * 2);      // one shift-add per address
                         const unsigned *x1 = (const unsigned *)(s2x[u] + p * XPLANE + o1 * 2);
                         d[u][p] = (nf4){__uint_as_float(x0[0]), __uint_as_float(x0[1]), __uint_as_float(x1[0]), __uint_as_float(x1[1])};
@@ -411,16 +414,18 @@ __global__ __launch_bounds__(NCF_THREADS, 1) void nc_fused_kernel(NcFusedArgs a)
 #endif
 #pragma unroll
             for (int sl = 0; sl < 7; ++sl) {
-                nf4 (&c)[2][2] = xv[sl & 1];
+                nf4 (&c)[2][NP] = xv[sl & 1];
                 if (sl < 6) frags(sl + 1, xv[(sl + 1) & 1]);
-                acc[0] = NCF_MFMA32(w1[sl][0], c[0][1], acc[0]); acc[1] = NCF_MFMA32(w1[sl][0], c[1][1], acc[1]);
-                acc[0] = NCF_MFMA32(w1[sl][1], c[0][0], acc[0]); acc[1] = NCF_MFMA32(w1[sl][1], c[1][0], acc[1]);
+                if constexpr (NP == 2) {
+                    acc[0] = NCF_MFMA32(w1[sl][0], c[0][1], acc[0]); acc[1] = NCF_MFMA32(w1[sl][0], c[1][1], acc[1]);
+                    acc[0] = NCF_MFMA32(w1[sl][1], c[0][0], acc[0]); acc[1] = NCF_MFMA32(w1[sl][1], c[1][0], acc[1]);
+                }
                 acc[0] = NCF_MFMA32(w1[sl][0], c[0][0], acc[0]); acc[1] = NCF_MFMA32(w1[sl][0], c[1][0], acc[1]);
                 // order inside the slab: its first MFMA leads, the address arithmetic and the eight reads of the next slab's
                 // fragments follow in the shadow of the MFMAs (a matrix instruction occupies its pipe for 32 cycles, the
-                // vector ALU is free meanwhile)
+                // vector ALU is free meanwhile; one plane: two MFMAs and four reads per slab)
 #pragma unroll
-                for (int q = 0; q < 6; ++q) {
+                for (int q = 0; q < (NP == 2 ? 6 : 2); ++q) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
                     __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
@@ -444,14 +449,16 @@ __global__ __launch_bounds__(NCF_THREADS, 1) void nc_fused_kernel(NcFusedArgs a)
                         const nf2 hv = __builtin_elementwise_fma(av, sv, bv);
                         h[2 * j] = fmaxf(hv[0], 0.f); h[2 * j + 1] = fmaxf(hv[1], 0.f);
                     }
-                    unsigned p0[4], p1[4];
+                    unsigned p0[4];
+                    [[maybe_unused]] unsigned p1[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         p0[j] = npk(h[2 * j], h[2 * j + 1]);
-                        p1[j] = npk(h[2 * j] - npk_lo(p0[j]), h[2 * j + 1] - npk_hi(p0[j]));
+                        if constexpr (NP == 2) p1[j] = npk(h[2 * j] - npk_lo(p0[j]), h[2 * j + 1] - npk_hi(p0[j]));
                     }
                     *(nf4 *)(dst + kh * HKH) = (nf4){__uint_as_float(p0[0]), __uint_as_float(p0[1]), __uint_as_float(p0[2]), __uint_as_float(p0[3])};
-                    *(nf4 *)(dst + kh * HKH + HPLANE) = (nf4){__uint_as_float(p1[0]), __uint_as_float(p1[1]), __uint_as_float(p1[2]), __uint_as_float(p1[3])};
+                    if constexpr (NP == 2)
+                        *(nf4 *)(dst + kh * HKH + HPLANE) = (nf4){__uint_as_float(p1[0]), __uint_as_float(p1[1]), __uint_as_float(p1[2]), __uint_as_float(p1[3])};
                 }
             }
         }
@@ -482,8 +489,8 @@ __global__ __launch_bounds__(NCF_THREADS, 1) void nc_fused_kernel(NcFusedArgs a)
                     nf4 accA = {0.f, 0.f, 0.f, 0.f}, accB = {0.f, 0.f, 0.f, 0.f};
                     nf4 fr[2][4];
                     auto frags3 = [&](int st, nf4 (&d)[4]) {
-                        d[0] = *(const nf4 *)(ha + s3off[st]); d[1] = *(const nf4 *)(ha + s3off[st] + HPLANE);
-                        d[2] = *(const nf4 *)(hb + s3off[st]); d[3] = *(const nf4 *)(hb + s3off[st] + HPLANE);
+                        d[0] = *(const nf4 *)(ha + s3off[st]); d[2] = *(const nf4 *)(hb + s3off[st]);
+                        if constexpr (NP == 2) { d[1] = *(const nf4 *)(ha + s3off[st] + HPLANE); d[3] = *(const nf4 *)(hb + s3off[st] + HPLANE); }
                     };
                     frags3(0, fr[0]);
 #pragma unroll
@@ -491,8 +498,10 @@ __global__ __launch_bounds__(NCF_THREADS, 1) void nc_fused_kernel(NcFusedArgs a)
                         nf4 (&c)[4] = fr[st & 1];
                         if (st < 4) frags3(st + 1, fr[(st + 1) & 1]);
                         __builtin_amdgcn_sched_barrier(0);
-                        accA = NCF_MFMA16(c[1], w2[st][0], accA); accB = NCF_MFMA16(c[3], w2[st][0], accB);
-                        accA = NCF_MFMA16(c[0], w2[st][1], accA); accB = NCF_MFMA16(c[2], w2[st][1], accB);
+                        if constexpr (NP == 2) {
+                            accA = NCF_MFMA16(c[1], w2[st][0], accA); accB = NCF_MFMA16(c[3], w2[st][0], accB);
+                            accA = NCF_MFMA16(c[0], w2[st][1], accA); accB = NCF_MFMA16(c[2], w2[st][1], accB);
+                        }
                         accA = NCF_MFMA16(c[0], w2[st][0], accA); accB = NCF_MFMA16(c[2], w2[st][0], accB);
                         __builtin_amdgcn_sched_barrier(0);
                     }
@@ -515,8 +524,8 @@ __global__ __launch_bounds__(NCF_THREADS, 1) void nc_fused_kernel(NcFusedArgs a)
                 // the fragments of step st + 1 are read while the six MFMAs of step st issue (order pinned by sched_barrier)
                 nf4 fr[2][4];                                  // [buffer][a plane 0, a plane 1, b plane 0, b plane 1]
                 auto frags3 = [&](int st, nf4 (&d)[4]) {
-                    d[0] = *(const nf4 *)(ha + s3off[st]); d[1] = *(const nf4 *)(ha + s3off[st] + HPLANE);
-                    d[2] = *(const nf4 *)(hb + s3off[st]); d[3] = *(const nf4 *)(hb + s3off[st] + HPLANE);
+                    d[0] = *(const nf4 *)(ha + s3off[st]); d[2] = *(const nf4 *)(hb + s3off[st]);
+                    if constexpr (NP == 2) { d[1] = *(const nf4 *)(ha + s3off[st] + HPLANE); d[3] = *(const nf4 *)(hb + s3off[st] + HPLANE); }
                 };
                 frags3(0, fr[0]);
 #pragma unroll
@@ -524,8 +533,10 @@ __global__ __launch_bounds__(NCF_THREADS, 1) void nc_fused_kernel(NcFusedArgs a)
                     nf4 (&c)[4] = fr[st & 1];
                     if (st < 4) frags3(st + 1, fr[(st + 1) & 1]);
                     __builtin_amdgcn_sched_barrier(0);
-                    accA = NCF_MFMA16(c[1], w2[st][0], accA); accB = NCF_MFMA16(c[3], w2[st][0], accB);
-                    accA = NCF_MFMA16(c[0], w2[st][1], accA); accB = NCF_MFMA16(c[2], w2[st][1], accB);
+                    if constexpr (NP == 2) {
+                        accA = NCF_MFMA16(c[1], w2[st][0], accA); accB = NCF_MFMA16(c[3], w2[st][0], accB);
+                        accA = NCF_MFMA16(c[0], w2[st][1], accA); accB = NCF_MFMA16(c[2], w2[st][1], accB);
+                    }
                     accA = NCF_MFMA16(c[0], w2[st][0], accA); accB = NCF_MFMA16(c[2], w2[st][0], accB);
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -729,7 +740,7 @@ static long nc_fused_tile(NcFusedArgs &a, int pairs, const int *forced) {
 }
 
 int launch_nc_fused(const float *X, float *Y, float *Y2, size_t stride, int pairs, int d0, int d1, int d2, int d3,
-                    const unsigned char *w_dev, float b2, const int *xmax, size_t xmax_stride, const int *forced_tile,
+                    const unsigned char *w_dev, float b2, const int *xmax, size_t xmax_stride, const int *forced_tile, int planes,
                     hipStream_t stream) {
     // the flush computes output offsets in 32 bits
     P2P_REQUIRE((unsigned long long)d0 * d1 * d2 * d3 < (1ull << 31), P2P_EUNSUPPORTED,
@@ -742,17 +753,16 @@ int launch_nc_fused(const float *X, float *Y, float *Y2, size_t stride, int pair
     P2P_REQUIRE(a.P <= 64 && lds <= NCF_LDS_MAX && a.tc + 4 <= 12 && (a.tc + 2) * a.P <= 512, P2P_EUNSUPPORTED,
                 "consensus tile does not fit (P %d, tc %d, LDS %zu)", a.P, a.tc, lds);
     static DeviceOnce attr_set;
-    const int dev = raise_lds_limit(attr_set, {{(const void *)nc_fused_kernel<0>, (int)NCF_LDS_MAX}, {(const void *)nc_fused_kernel<5>, (int)NCF_LDS_MAX},
-                                               {(const void *)nc_fused_kernel<10>, (int)NCF_LDS_MAX}});
+    const int dev = raise_lds_limit(attr_set, {{(const void *)nc_fused_kernel<0, 2>, (int)NCF_LDS_MAX}, {(const void *)nc_fused_kernel<5, 2>, (int)NCF_LDS_MAX},
+                                               {(const void *)nc_fused_kernel<10, 2>, (int)NCF_LDS_MAX}, {(const void *)nc_fused_kernel<0, 1>, (int)NCF_LDS_MAX},
+                                               {(const void *)nc_fused_kernel<5, 1>, (int)NCF_LDS_MAX}, {(const void *)nc_fused_kernel<10, 1>, (int)NCF_LDS_MAX}});
     if (dev < 0) return dev;
     const dim3 grid(a.na * a.nb * a.nc * a.nd, 1, pairs);                  // one work-group per tile: both branches
     const bool fixed = a.tc == 8 && a.td == 40 && a.P == 44;
-    if (fixed && a.tb == 10)
-        hipLaunchKernelGGL(nc_fused_kernel<10>, grid, dim3(NCF_THREADS), lds, stream, a);
-    else if (fixed && a.tb == 5)
-        hipLaunchKernelGGL(nc_fused_kernel<5>, grid, dim3(NCF_THREADS), lds, stream, a);
-    else
-        hipLaunchKernelGGL(nc_fused_kernel<0>, grid, dim3(NCF_THREADS), lds, stream, a);
+    const int ftb = fixed && (a.tb == 10 || a.tb == 5) ? a.tb : 0;
+    const auto kernel = planes == 1 ? (ftb == 10 ? nc_fused_kernel<10, 1> : ftb == 5 ? nc_fused_kernel<5, 1> : nc_fused_kernel<0, 1>)
+                                    : (ftb == 10 ? nc_fused_kernel<10, 2> : ftb == 5 ? nc_fused_kernel<5, 2> : nc_fused_kernel<0, 2>);
+    hipLaunchKernelGGL(kernel, grid, dim3(NCF_THREADS), lds, stream, a);
     return check_launch("nc_fused_kernel");
 }
 

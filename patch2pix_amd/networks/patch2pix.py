@@ -174,6 +174,8 @@ class Patch2Pix(nn.Module):
             sd = self.state_dict()
             ncn = ops.NcnWeights.from_state_dict({k[len("ncn."):]: v for k, v in sd.items() if k.startswith("ncn.")}, self.device,
                                                  symmetric_mode=self._ncn_layout["symmetric_mode"])
+            if getattr(self, "_coarse_mode", None) is not None:       # the new handle starts in the default mode
+                ncn.set_mode(self._coarse_mode)
             mid = fine = None
             if self.regress_mid is not None:
                 sub = lambda p: {k[len(p):]: v for k, v in sd.items() if k.startswith(p)}
@@ -182,6 +184,26 @@ class Patch2Pix(nn.Module):
                                                                     self.regressor_config, self.feat_idx)
             self._packed = (ncn, mid, fine)
         return self._packed
+
+    def set_coarse_mode(self, mode):
+        """'fp16x2' (default, fp32-equivalent) or the opt-in 'fp16' for the matrix-core kernels of the coarse stage (one fp16
+        plane per operand, one MFMA product per product: NOT fp32-equivalent, see ops.NcnWeights.set_mode).  The choice belongs
+        to the model: it is applied to the packed consensus handle now and again whenever the weights are re-packed
+        (load_state_dict, init_weights_).  A model with a generic consensus stack raises NotImplementedError."""
+        ops.coarse_mode_id(mode)                                    # ValueError for an unknown name, before anything changes
+        if self._ncn_layout != ops.RELEASED_NCN_LAYOUT:
+            raise NotImplementedError("set_coarse_mode: a generic consensus stack runs exact fp32 kernels and has no modes")
+        self._coarse_mode = mode
+        if self._packed is not None:
+            self._packed[0].set_mode(mode)
+
+    @property
+    def coarse_mode(self):
+        """The mode `set_coarse_mode` chose, or the one new handles start in (P2P_COARSE_MODE, else 'fp16x2'); 'fp16x2' for a
+        generic consensus stack."""
+        if self._ncn_layout != ops.RELEASED_NCN_LAYOUT:
+            return "fp16x2"
+        return getattr(self, "_coarse_mode", None) or ops.default_coarse_mode()
 
     # ------------------------------------------------------------------ coarse stage
     def forward_coarse_match(self, feat1, feat2, ksize=1):

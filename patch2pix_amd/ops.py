@@ -84,6 +84,18 @@ def ncn_shapes(lay):
     return shapes
 
 
+def coarse_mode_id(mode):
+    """'fp16x2' | 'fp16' -> P2P_COARSE_FP16X2 | P2P_COARSE_FP16 (include/p2p_hip.h); anything else raises ValueError."""
+    if not isinstance(mode, str) or mode not in _lib.COARSE_MODES:
+        raise ValueError(f"unknown coarse mode {mode!r}: one of {sorted(_lib.COARSE_MODES)}")
+    return _lib.COARSE_MODES[mode]
+
+
+def default_coarse_mode():
+    """The mode new tuned NcnWeights handles start in: P2P_COARSE_MODE=fp16x2|fp16 (tools; read here, not in the library)."""
+    return os.environ.get("P2P_COARSE_MODE") or "fp16x2"
+
+
 class NcnWeights:
     """Device-resident NeighConsensus filters (reference networks/ncn/model.py:124-143).  The constructor takes the released
     stack's four tensors (the tuned kernel); `from_state_dict` takes any stack within `ncn_layout`'s limits."""
@@ -98,6 +110,8 @@ class NcnWeights:
         with torch.cuda.device(device):
             _lib.check(_lib.p2p_ncn_create(*[t.data_ptr() for t in keep], ctypes.byref(self.handle)), "p2p_ncn_create")
         self.device = torch.device(device)
+        if default_coarse_mode() != "fp16x2":
+            self.set_mode(default_coarse_mode())
 
     @classmethod
     def from_state_dict(cls, sd, device, symmetric_mode=True, generic=False):
@@ -126,6 +140,22 @@ class NcnWeights:
         if self.generic:
             raise NotImplementedError("set_tile: a generic consensus handle has no work-group tile to force")
         _lib.check(_lib.p2p_ncn_set_tile(self.handle, int(ta), int(tb), int(tc)), "p2p_ncn_set_tile")
+
+    def set_mode(self, mode):
+        """'fp16x2' (default: fp32-equivalent, two fp16 planes per operand, 3 MFMA products) or the opt-in 'fp16': the matrix-core
+        kernels of every coarse-stage call with this handle (feature preparation, correlation + pooling, the fused consensus
+        kernel) run with ONE fp16 plane per operand and one MFMA product -- relative operand rounding 2^-11, NOT
+        fp32-equivalent ("Single-plane mode of the coarse stage").  Nothing is packed or uploaded.  A
+        generic handle (exact fp32 kernels) has no modes: NotImplementedError."""
+        mid = coarse_mode_id(mode)
+        if self.generic:
+            raise NotImplementedError("set_mode: a generic consensus handle runs exact fp32 kernels and has no modes")
+        _lib.check(_lib.p2p_ncn_set_mode(self.handle, mid), "p2p_ncn_set_mode")
+
+    @property
+    def mode(self):
+        mid = _lib.p2p_ncn_get_mode(self.handle)
+        return next(k for k, v in _lib.COARSE_MODES.items() if v == mid)
 
     def __del__(self):
         if getattr(self, "handle", None) and _lib is not None:      # _lib is None during interpreter shutdown

@@ -14,8 +14,8 @@ pair.
 Outputs are the lists `predict_fine` returns (batch item -> [n,4] fp32, [n] fp32, [n,4] int64).  Not available for the
 training-time options (ptmax, panc > 1): those draw from the host's numpy RNG (networks/utils.py:55-63).
 
-A capture records the kernels of the modes in force when it is made: after `net.extract.set_mode(...)` (or a regressor's
-`set_mode`) an existing GraphedMatcher goes on replaying the OLD arithmetic.  Nothing detects this; choose the modes first, or
+A capture records the kernels of the modes in force when it is made: after `net.extract.set_mode(...)`,
+`net.set_coarse_mode(...)` (or a regressor's `set_mode`) an existing GraphedMatcher goes on replaying the OLD arithmetic.  Nothing detects this; choose the modes first, or
 make a new GraphedMatcher after a change.
 """
 import torch
