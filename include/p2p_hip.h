@@ -210,7 +210,12 @@ size_t p2p_neigh_consensus_workspace_bytes(const p2p_ncn *ncn, int hA, int wA, i
  *              reference's slice order (modules.py:13-18); may be NULL; ignored when ksize == 1
  * ksize must be 1, 2 (the reference's default in predict_*) or 4 (maxpool4d's own default; since version 103);
  * other values -> P2P_EUNSUPPORTED (k^4 codes must fit the byte: 4 is the last value that does).  Feature map sides
- * must be multiples of ksize (P2P_EINVAL otherwise).                                              */
+ * must be multiples of ksize (P2P_EINVAL otherwise).
+ * channels: a multiple of 32 up to 1024 (P2P_EUNSUPPORTED otherwise) -- 256 for ResNet34, 1024 for ResNet50 / ResNet101
+ * truncated after layer3 (NCNet's own configuration); in both coarse modes.  Above 256 channels the feature-preparation
+ * kernel keeps a position's channels in dynamic LDS sized by the channel count; the sum of squares is one fixed-order fp32
+ * reduction per position at every width, so a pair's result does not depend on its batch mates or on the tiling.  Up to
+ * 256 channels the buffers and results are bit for bit those of the versions that stopped there.             */
 int p2p_coarse_forward(const float *featA, const float *featB, int channels, int hA, int wA, int hB, int wB,
                        int ksize, const p2p_ncn *ncn, float *corr4d_out, uint8_t *delta_out,
                        void *workspace, size_t workspace_bytes, p2p_stream_t stream);
@@ -509,12 +514,13 @@ int p2p_regress_batch_dev(const p2p_regressor *reg1, const p2p_regressor *reg2, 
                           float *matches2, float *probs2, float *raw2,
                           void *workspace, size_t workspace_bytes, p2p_stream_t stream);
 
-/* ---- feature-pyramid producer (the convolutions of ResNet34 layer1..layer3) ------------------ */
+/* ---- feature-pyramid producer (the convolutions of ResNet34 / 50 / 101 layer1..layer3) ------- */
 
 /* One Conv2d(ci, co, ks, stride, padding = ks / 2, bias = False) + BatchNorm2d(co) in eval mode -- reference
- * networks/resnet.py:26-60 (BasicBlock: conv1/bn1, conv2/bn2, downsample) as used by forward_all (:138-157) with the
- * layer3 stride patch (:169-173).  HOST pointers: weight [co,ci,ks,ks], the four BatchNorm vectors [co].  Supported:
- * ks 1 or 3, stride 1 or 2, ci a multiple of 32, co a multiple of 64 (every convolution of layer1..layer3).
+ * networks/resnet.py:26-100 (BasicBlock: conv1/bn1, conv2/bn2, downsample; Bottleneck: conv1..conv3, downsample) as used by
+ * forward_all (:138-157) with or without the layer3 stride patch (:169-173).  HOST pointers: weight [co,ci,ks,ks], the four
+ * BatchNorm vectors [co].  Supported: ks 1 or 3, stride 1 or 2, ci a multiple of 32, co a multiple of 64 (of 128 at stride 2):
+ * every convolution of layer1..layer3 of the three backbones, up to 1024 channels on either side.
  * Arithmetic: fp32-equivalent (operands as two fp16 planes under exact power-of-two scales, three MFMA products per
  * fp32 product, fp32 accumulation).                                                                             */
 typedef struct p2p_conv p2p_conv;

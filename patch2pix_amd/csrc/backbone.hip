@@ -521,7 +521,8 @@ extern "C" int p2p_conv_set_tile(p2p_conv *cv, int mt, int nt, int wn) {
 extern "C" int p2p_conv_create(const float *weight, const p2p_bn_params *bn, int ci, int co, int ks, int stride, p2p_conv **out) {
     P2P_REQUIRE(weight && bn && out, P2P_EINVAL, "p2p_conv_create: null argument");
     P2P_REQUIRE((ks == 1 || ks == 3) && (stride == 1 || stride == 2) && ci % 32 == 0 && co % 64 == 0, P2P_EUNSUPPORTED,
-                "p2p_conv_create: %dx%d stride %d, %d -> %d channels is outside the ResNet34 layers this library covers", ks, ks, stride, ci, co);
+                "p2p_conv_create: %dx%d stride %d, %d -> %d channels: 1x1 or 3x3, stride 1 or 2, input channels a multiple of 32, output channels a multiple of 64 "
+                "(the BasicBlock and Bottleneck layers of ResNet34 / 50 / 101 up to layer3)", ks, ks, stride, ci, co);
     P2P_REQUIRE(stride == 1 || co % 128 == 0, P2P_EUNSUPPORTED, "p2p_conv_create: stride 2 with %d output channels", co);
     const int ck = conv_ck(stride), nchunks = ci / ck, spc = ck / 16, nsl = ks * ks * spc, ntiles = co / 32;
     const size_t wbytes = ((size_t)nchunks * nsl + 3) * ntiles * 2048;      // + the slabs of zeros the prefetch runs into

@@ -55,7 +55,13 @@ __device__ __forceinline__ int prep_row_k4(int pp) { return (pp & ~31) + (pp & 3
 // (PERM_A = the k = 4 instantiation: a template parameter, so that the kernel of k = 1, 2 is the code it was without it)
 // NP = planes per operand: 2 = the fp32-equivalent split (default), 1 = the single-plane mode P2P_COARSE_FP16 -- the first plane
 // alone (one rounding to fp16, 2^-11 relative), in blocks of half the size: [row 128][4 pieces of 8 ch] = 8 KB per K chunk.
-template <bool PERM_A, int NP = 2>
+// WIDE: the tile of C > 256 channels (the 512 / 1024 of a Bottleneck backbone) lives in dynamic LDS sized by C (68 KB at 1024:
+// two work-groups per compute unit); C <= 256 keeps the static 17 KB tile and is the instantiation it always was, so its buffers
+// keep their bits.  The code is the same: the whole channel column of a position is resident, so the sum of squares stays ONE
+// fixed-order fp32 reduction per position (16 strided partial sums in ascending channel order, then their sum in ascending group
+// order) whatever C, batch and tiling.
+constexpr int PREP_C_STATIC = 256, PREP_C_MAX = 1024;
+template <bool PERM_A, int NP = 2, bool WIDE = false>
 __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     const int img = blockIdx.y;
     if (img == 0) {
@@ -79,7 +85,12 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
             *(f32x4 *)d = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
     }
-    __shared__ float tile[256 * (PREP_P + 1)];   // [C <= 256][17]
+    __shared__ float tile_static[(WIDE ? 1 : PREP_C_STATIC) * (PREP_P + 1)];   // [C <= 256][17]
+    float *tile = tile_static;
+    if constexpr (WIDE) {
+        P2P_DYN_SHARED(float, tile_wide);                                      // [C <= 1024][17]
+        tile = tile_wide;
+    }
     __shared__ float part[16][PREP_P];
     __shared__ float inv[PREP_P];
     const int hw = h * w;
@@ -131,11 +142,27 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     }
 }
 
-void launch_prep(const PrepArgs &a, int planes, unsigned nz, hipStream_t stream) {
+int launch_prep(const PrepArgs &a, int planes, unsigned nz, hipStream_t stream) {
     const int gp = std::max(ceil_div(std::max(a.h[0] * a.w[0], a.h[1] * a.w[1]), PREP_P), ceil_div(a.nkeys + 1, 256));
+    if (a.C > PREP_C_STATIC) {
+        if (a.C > PREP_C_MAX) {
+            set_error("launch_prep: %d channels (at most %d)", a.C, PREP_C_MAX);
+            return P2P_EUNSUPPORTED;
+        }
+        constexpr int lds_max = PREP_C_MAX * (PREP_P + 1) * (int)sizeof(float);
+        static DeviceOnce attr_set;
+        const int dev = raise_lds_limit(attr_set, {{(const void *)prep_kernel<true, 1, true>, lds_max}, {(const void *)prep_kernel<false, 1, true>, lds_max},
+                                                   {(const void *)prep_kernel<true, 2, true>, lds_max}, {(const void *)prep_kernel<false, 2, true>, lds_max}});
+        if (dev < 0) return dev;
+        const auto kernel = planes == 1 ? (a.k == 4 ? prep_kernel<true, 1, true> : prep_kernel<false, 1, true>)
+                                        : (a.k == 4 ? prep_kernel<true, 2, true> : prep_kernel<false, 2, true>);
+        hipLaunchKernelGGL(kernel, dim3(gp, 2, nz), dim3(256), (size_t)a.C * (PREP_P + 1) * sizeof(float), stream, a);
+        return P2P_OK;
+    }
     const auto kernel = planes == 1 ? (a.k == 4 ? prep_kernel<true, 1> : prep_kernel<false, 1>)
                                     : (a.k == 4 ? prep_kernel<true, 2> : prep_kernel<false, 2>);
     hipLaunchKernelGGL(kernel, dim3(gp, 2, nz), dim3(256), 0, stream, a);
+    return P2P_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -206,7 +233,13 @@ __device__ __forceinline__ f32x16 cx_mfma(const f32x4 &a, const f32x4 &b, const 
     if constexpr (NP == 2) __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                          \
     __builtin_amdgcn_sched_barrier(0);
 
-template <int KS, int NP = 2>
+// WIDE (C > 256): the matrix cores add into an accumulator chain of 6 (NP = 2) products per stage, and the error of that chain
+// grows with its length (measured at 1024 channels: the volume 2.5 - 4.5 x as far from fp64 as an fp32 GEMM's, against 1.5 x at
+// 256).  Every CX_FLUSH stages the accumulators are therefore added (VALU fp32, round to nearest) into a second set and start
+// again from zero: chains of at most CX_FLUSH stages whatever C, their sums added in ascending K order -- the same fixed order
+// for every tile, pair and batch.  C <= 256 is the instantiation without the second set: its arithmetic and bits are unchanged.
+constexpr int CX_FLUSH = 4;
+template <int KS, int NP = 2, bool WIDE = false>
 __global__ __launch_bounds__(256, 2) void corr_pool_kernel(const unsigned short *__restrict__ A, const unsigned short *__restrict__ B,
                                                            int nA, int nB, int C, float *__restrict__ P,
                                                            uint8_t *__restrict__ delta, size_t sAB, size_t sP, size_t sDelta,
@@ -256,9 +289,24 @@ __global__ __launch_bounds__(256, 2) void corr_pool_kernel(const unsigned short 
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = (f32x16){0};
 
+    f32x16 tot[WIDE ? 2 : 1][WIDE ? 2 : 1];
+    if constexpr (WIDE) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) tot[i][j] = (f32x16){0};
+    }
     f32x4 xa[2][NP], xb[2][NP], ya[2][NP], yb[2][NP];
 #pragma unroll 1
     for (int it = 0; it < nk; it += 2) {
+        if constexpr (WIDE) {
+            if (it && (it & (CX_FLUSH - 1)) == 0) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) { tot[i][j] += acc[i][j]; acc[i][j] = (f32x16){0}; }
+            }
+        }
         // even stage (slot 0): its pieces have landed for everybody behind the barrier, and everybody is done with slot 1
         P2P_WAIT_VMCNT(0);
         __builtin_amdgcn_s_barrier();
@@ -284,6 +332,12 @@ __global__ __launch_bounds__(256, 2) void corr_pool_kernel(const unsigned short 
         CX_PIPE()
         CX_SLAB(ya, yb)
         __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (WIDE) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = tot[i][j] + acc[i][j];
     }
     // the next tile of this work-group: its stage 0 goes to slot 0 behind a barrier (everybody is done reading the ring)
     const int rowA0c = rowA0, rowB0c = rowB0;
@@ -428,7 +482,10 @@ int launch_corr_pool(const unsigned short *fnA, const unsigned short *fnB, int n
     static DeviceOnce attr_set_dev;      // per device: a process may drive several GPUs
     const int dev = raise_lds_limit(attr_set_dev, {{(const void *)corr_pool_kernel<1, 2>, cx_lds(2)}, {(const void *)corr_pool_kernel<2, 2>, cx_lds(2)},
                                                    {(const void *)corr_pool_kernel<4, 2>, cx_lds(2)}, {(const void *)corr_pool_kernel<1, 1>, cx_lds(1)},
-                                                   {(const void *)corr_pool_kernel<2, 1>, cx_lds(1)}, {(const void *)corr_pool_kernel<4, 1>, cx_lds(1)}});
+                                                   {(const void *)corr_pool_kernel<2, 1>, cx_lds(1)}, {(const void *)corr_pool_kernel<4, 1>, cx_lds(1)},
+                                                   {(const void *)corr_pool_kernel<1, 2, true>, cx_lds(2)}, {(const void *)corr_pool_kernel<2, 2, true>, cx_lds(2)},
+                                                   {(const void *)corr_pool_kernel<4, 2, true>, cx_lds(2)}, {(const void *)corr_pool_kernel<1, 1, true>, cx_lds(1)},
+                                                   {(const void *)corr_pool_kernel<2, 1, true>, cx_lds(1)}, {(const void *)corr_pool_kernel<4, 1, true>, cx_lds(1)}});
     if (dev < 0) return dev;
     const int gx = ceil_div(nB, CT), gy = ceil_div(nA, CT);
     const long long ntiles = (long long)gx * gy * nz;
@@ -437,8 +494,11 @@ int launch_corr_pool(const unsigned short *fnA, const unsigned short *fnB, int n
     const int per_xcd = (int)((ntiles + 7) / 8);
     const dim3 cgrid((unsigned)(8 * std::min(per_xcd, 64)));
     if (ksize == 1) delta = nullptr, sDelta = 0;       // nothing was pooled: no argmax to record
-    const auto kernel = planes == 1 ? (ksize == 1 ? corr_pool_kernel<1, 1> : (ksize == 4 ? corr_pool_kernel<4, 1> : corr_pool_kernel<2, 1>))
-                                    : (ksize == 1 ? corr_pool_kernel<1, 2> : (ksize == 4 ? corr_pool_kernel<4, 2> : corr_pool_kernel<2, 2>));
+    const auto kernel = C > 256
+        ? (planes == 1 ? (ksize == 1 ? corr_pool_kernel<1, 1, true> : (ksize == 4 ? corr_pool_kernel<4, 1, true> : corr_pool_kernel<2, 1, true>))
+                       : (ksize == 1 ? corr_pool_kernel<1, 2, true> : (ksize == 4 ? corr_pool_kernel<4, 2, true> : corr_pool_kernel<2, 2, true>)))
+        : (planes == 1 ? (ksize == 1 ? corr_pool_kernel<1, 1> : (ksize == 4 ? corr_pool_kernel<4, 1> : corr_pool_kernel<2, 1>))
+                       : (ksize == 1 ? corr_pool_kernel<1, 2> : (ksize == 4 ? corr_pool_kernel<4, 2> : corr_pool_kernel<2, 2>)));
     hipLaunchKernelGGL(kernel, cgrid, dim3(256), cx_lds(planes), stream, fnA, fnB, nA, nB, C, P, delta, sAB, sP, sDelta, gx, gy, (int)ntiles, per_xcd);
     return P2P_OK;
 }

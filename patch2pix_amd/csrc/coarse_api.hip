@@ -100,7 +100,7 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
     P2P_REQUIRE(featA && featB && ncn && corr4d_out && workspace, P2P_EINVAL, "p2p_coarse_forward: null argument");
     P2P_REQUIRE(batch >= 1 && batch <= 65535, P2P_EINVAL, "p2p_coarse_forward: batch %d out of range", batch);
     P2P_REQUIRE(ksize == 1 || ksize == 2 || ksize == 4, P2P_EUNSUPPORTED, "p2p_coarse_forward: ksize %d not supported (1, 2 or 4)", ksize);
-    P2P_REQUIRE(C > 0 && C % 32 == 0 && C <= 256, P2P_EUNSUPPORTED, "p2p_coarse_forward: channels %d (multiple of 32, <= 256)", C);
+    P2P_REQUIRE(C > 0 && C % 32 == 0 && C <= 1024, P2P_EUNSUPPORTED, "p2p_coarse_forward: channels %d (multiple of 32, <= 1024)", C);
     P2P_REQUIRE(hA > 0 && wA > 0 && hB > 0 && wB > 0 && hA % ksize == 0 && wA % ksize == 0 && hB % ksize == 0 &&
                     wB % ksize == 0, P2P_EINVAL, "p2p_coarse_forward: feature map sizes must be positive multiples of ksize");
     // The handle is dereferenced only after the workspace has passed the size every kind of handle needs: callers probe this
@@ -131,9 +131,10 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
         int *rkey1 = (int *)(base + ws.keys), *ckey1 = rkey1 + nAc, *rkey2 = ckey1 + nBc, *ckey2 = rkey2 + nAc;
         const int nkeys = 2 * (nAc + nBc);
         int *xmax = rkey1 + nkeys;
-        launch_prep(PrepArgs{{fA, fB}, {fnA, fnB}, {hA, hB}, {wA, wB}, {(size_t)C * nA, (size_t)C * nB}, C, ksize, 2 * sWs, rkey1, nkeys, sWs},
-                    planes, nz, stream);
-        int st = launch_corr_pool(fnA, fnB, nA, nB, C, ksize, planes, P, dout, 2 * sWs, sWs, nel, nz, stream);
+        int st = launch_prep(PrepArgs{{fA, fB}, {fnA, fnB}, {hA, hB}, {wA, wB}, {(size_t)C * nA, (size_t)C * nB}, C, ksize, 2 * sWs, rkey1, nkeys, sWs},
+                             planes, nz, stream);
+        if (st != P2P_OK) return st;
+        st = launch_corr_pool(fnA, fnB, nA, nB, C, ksize, planes, P, dout, 2 * sWs, sWs, nel, nz, stream);
         if (st != P2P_OK) return st;
         launch_maxima(P, nAc, nBc, rkey1, ckey1, sWs, sWs, nullptr, nz, stream);
         // first mutual matching, in place on the pooled volume (+ max |X| for the consensus kernel's operand scale)

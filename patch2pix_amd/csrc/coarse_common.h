@@ -22,7 +22,8 @@ struct PrepArgs {
     size_t sKeys;
 };
 // planes: fp16 planes per operand, 2 (P2P_COARSE_FP16X2) or 1 (P2P_COARSE_FP16) -- the same for the three matrix-core launchers
-void launch_prep(const PrepArgs &a, int planes, unsigned nz, hipStream_t stream);
+// C: a multiple of 32 up to 1024 (above 256 the tile is dynamic LDS sized by C)
+int launch_prep(const PrepArgs &a, int planes, unsigned nz, hipStream_t stream);
 // delta: the argmax codes (ksize > 1; optional); sAB / sP / sDelta: per-pair strides of the feature planes, of P and of delta
 int launch_corr_pool(const unsigned short *fnA, const unsigned short *fnB, int nA, int nB, int C, int ksize, int planes, float *P,
                      uint8_t *delta, size_t sAB, size_t sP, size_t sDelta, unsigned nz, hipStream_t stream);

@@ -16,6 +16,29 @@ from .utils import filter_coarse
 from .. import ops, staging
 
 
+BACKBONES = ("ResNet34", "ResNet50", "ResNet101")      # what `config.backbone` may name (reference networks/resnet.py:175-191)
+REGRESSOR_FEAT_DIMS = (3, 64, 64, 128, 256)            # what the reference builds its regressors for, whatever the backbone (patch2pix.py:20)
+
+
+def backbone_layout(backbone, change_stride, feat_idx=None):
+    """What `Patch2Pix(config)` derives from the backbone's name and stride, checked without a GPU:
+    -> (class of networks/resnet.py, upsample, feats_downsample).  An unknown name raises NotImplementedError.  `feat_idx` (the
+    levels a regressor reads; None: no regressor) must name levels whose channel count is the reference's hard-coded one:
+    every level for ResNet34, levels 0 and 1 for the Bottleneck backbones -- ValueError otherwise, naming the level (the
+    reference fails there too, later, with a channel mismatch in its first regressor convolution)."""
+    if backbone not in BACKBONES:
+        raise NotImplementedError(f"backbone {backbone}: one of {', '.join(BACKBONES)} (reference networks/resnet.py:175-191)")
+    cls = getattr(resnet, backbone)
+    dims = [3, 64] + [planes * cls.block.expansion for _, planes, _, _ in cls.stages]
+    for lvl in (feat_idx or ()):
+        if 0 <= lvl < len(dims) and dims[lvl] != REGRESSOR_FEAT_DIMS[lvl]:
+            raise ValueError(f"feat_idx {list(feat_idx)}: level {lvl} of a {backbone} pyramid has {dims[lvl]} channels, the regressors "
+                             f"are built for {REGRESSOR_FEAT_DIMS[lvl]} (reference networks/patch2pix.py:20); use levels within "
+                             f"{{0, 1}} with this backbone")
+    # stride 8: layer3 keeps the resolution of layer2 (change_stride); else stride 16 -- levels 0..3 are the same either way
+    return cls, (8 if change_stride else 16), [1, 2, 2, 2, 1 if change_stride else 2]
+
+
 class _Holder(nn.Module):
     """Parameter container that reproduces a sub-tree of the reference state_dict."""
 
@@ -106,19 +129,13 @@ class Patch2Pix(nn.Module):
         if getattr(config, "training", False):
             raise NotImplementedError("training is out of scope of the MI355X matching path")
         self.backbone = config.backbone
-        if self.backbone != "ResNet34":
-            raise NotImplementedError(f"backbone {self.backbone}: only ResNet34 (the released model) is provided")
         self.change_stride = config.change_stride
-        self.upsample = 16
-        self.feats_downsample = [1, 2, 2, 2, 2]
-        feat_dims = [3, 64, 64, 128, 256]
-        self.extract = resnet.ResNet34()
+        cls, self.upsample, self.feats_downsample = backbone_layout(
+            self.backbone, self.change_stride, config.feat_idx if config.regressor_config else None)
+        feat_dims = list(REGRESSOR_FEAT_DIMS)
+        self.extract = cls()
         if self.change_stride:
             self.extract.change_stride(target="layer3")
-            self.upsample //= 2
-            self.feats_downsample[-1] = 1
-        else:
-            raise NotImplementedError("change_stride=False (upsample 16) is not implemented by the HIP fine stage")
         # what the library implements (include/p2p_hip.h, p2p_ncn_config): NotImplementedError / ValueError otherwise
         self._ncn_layout = _ncn_layout_of(config)
         self.ncn = _Holder(_ncn_spec(self._ncn_layout))

@@ -1,9 +1,9 @@
 """Feature-pyramid producer for the matching hot path.
 
-Role of reference networks/resnet.py:125-173 (ResNet34 truncated after layer3, with the
+Role of reference networks/resnet.py:125-191 (ResNet34, ResNet50 and ResNet101 truncated after layer3, with or without the
 layer3 stride patch of `change_stride`), SURVEY.md section 8 row f1.  The module keeps the torch
-parameters (checkpoints load unchanged); on the GPU in eval mode the 32 convolutions of
-stem and of layer1..layer3 run as the library's fp32-equivalent fp16 MFMA kernels (csrc/backbone.hip;
+parameters (checkpoints load unchanged); on the GPU in eval mode the convolutions of
+stem and of layer1..layer3 (32 for ResNet34, 43 for ResNet50, 94 for ResNet101) run as the library's fp32-equivalent fp16 MFMA kernels (csrc/backbone.hip;
 NHWC activations between the layers, NCHW pyramid levels out), the max-pool as its own kernel.
 `P2P_BACKBONE=miopen` selects the all-PyTorch path (the round-1/2 producer).  Parameter names follow the torchvision ResNet convention so that
 reference checkpoints (`extract.*` keys, utils/train/helper.py:10-17) load unchanged;
@@ -16,12 +16,16 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-# (planes, blocks, stride of first block) for ResNet34 up to layer3
-_STAGES = (("layer1", 64, 3, 1), ("layer2", 128, 4, 2), ("layer3", 256, 6, 2))
+# (planes, blocks, stride of first block) up to layer3
+_STAGES = (("layer1", 64, 3, 1), ("layer2", 128, 4, 2), ("layer3", 256, 6, 2))                  # ResNet34, ResNet50
+_STAGES101 = (("layer1", 64, 3, 1), ("layer2", 128, 4, 2), ("layer3", 256, 23, 2))
 
 
 class _Basic(nn.Module):
     """Two 3x3 conv+BN with identity / projected skip."""
+
+    expansion = 1
+    convs = (("conv1", "bn1"), ("conv2", "bn2"))       # in the order they run; the last one takes the skip
 
     def __init__(self, cin, cout, stride):
         super().__init__()
@@ -41,21 +45,54 @@ class _Basic(nn.Module):
         return F.relu(y + skip, inplace=True)
 
 
-class ResNet34(nn.Module):
-    """conv1/bn1 + layer1..layer3 of ResNet34; `pyramid()` returns the 5 maps the path reads."""
+class _Bottleneck(nn.Module):
+    """1x1 -> 3x3 (carries the stride) -> 1x1 to 4 x planes, conv+BN each, with identity / projected skip
+    (reference resnet.py:49-85)."""
+    expansion = 4
+    convs = (("conv1", "bn1"), ("conv2", "bn2"), ("conv3", "bn3"))
+
+    def __init__(self, cin, planes, stride):
+        super().__init__()
+        cout = planes * self.expansion
+        self.conv1 = nn.Conv2d(cin, planes, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, 3, stride, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.conv3 = nn.Conv2d(planes, cout, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(cout)
+        self.downsample = None
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False),
+                                            nn.BatchNorm2d(cout))
+
+    def forward(self, x):
+        skip = x if self.downsample is None else self.downsample(x)
+        y = F.relu(self.bn1(self.conv1(x)), inplace=True)
+        y = F.relu(self.bn2(self.conv2(y)), inplace=True)
+        y = self.bn3(self.conv3(y))
+        return F.relu(y + skip, inplace=True)
+
+
+class _ResNet(nn.Module):
+    """conv1/bn1 + layer1..layer3 of a ResNet; `pyramid()` returns the 5 maps the path reads.  The three backbones below differ
+    in the two class attributes only."""
+    block, stages = None, None
 
     def __init__(self):
         super().__init__()
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         cin = 64
-        for name, planes, blocks, stride in _STAGES:
-            seq = [_Basic(cin, planes, stride)] + [_Basic(planes, planes, 1) for _ in range(blocks - 1)]
+        for name, planes, blocks, stride in self.stages:
+            cout = planes * self.block.expansion
+            seq = [self.block(cin, planes, stride)] + [self.block(cout, planes, 1) for _ in range(blocks - 1)]
             setattr(self, name, nn.Sequential(*seq))
-            cin = planes
+            cin = cout
+        self.feat_dims = [3, 64] + [planes * self.block.expansion for _, planes, _, _ in self.stages]
 
     def change_stride(self, target="layer3"):
-        """Make `target`'s first block stride-1 (reference resnet.py:169-173)."""
+        """Make `target`'s first block stride-1 (reference resnet.py:169-173, literally: conv1, conv2 and downsample[0] -- in a
+        Bottleneck block conv1 is stride 1 already)."""
         blk = getattr(self, target)[0]
         for conv in (blk.conv1, blk.conv2, blk.downsample[0]):
             conv.stride = (1, 1)
@@ -74,10 +111,10 @@ class ResNet34(nn.Module):
         buffers() iterators cost a millisecond per call, more than launching the 36 kernels."""
         sig = [str(device)]
         pairs = [(self.conv1, self.bn1)]
-        for name, _, _, _ in _STAGES:
+        for name, _, _, _ in self.stages:
             for blk in self._modules[name]._modules.values():
                 m = blk._modules
-                pairs += [(m["conv1"], m["bn1"]), (m["conv2"], m["bn2"])]
+                pairs += [(m[c], m[b]) for c, b in self.block.convs]
                 if m.get("downsample") is not None:
                     d = m["downsample"]._modules
                     pairs.append((d["0"], d["1"]))
@@ -98,11 +135,12 @@ class ResNet34(nn.Module):
                     raise NotImplementedError(f"BatchNorm eps {bn.eps}: the HIP pyramid producer folds eps = 1e-5 (set P2P_BACKBONE=miopen)")
                 return ops.ConvBN(conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, conv.stride[0], device)
             trunk = []
-            for name, _, _, _ in _STAGES:
+            for name, _, _, _ in self.stages:
                 blocks = []
                 for blk in getattr(self, name):
                     down = pack(blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None
-                    blocks.append((pack(blk.conv1, blk.bn1), pack(blk.conv2, blk.bn2), down))
+                    # (the block's convolutions in the order they run ..., its projection or None)
+                    blocks.append(tuple(pack(getattr(blk, c), getattr(blk, b)) for c, b in blk.convs) + (down,))
                 trunk.append(blocks)
             if abs(self.bn1.eps - 1e-5) > 1e-12:
                 raise NotImplementedError(f"BatchNorm eps {self.bn1.eps}: the HIP pyramid producer folds eps = 1e-5 (set P2P_BACKBONE=miopen)")
@@ -152,15 +190,20 @@ class ResNet34(nn.Module):
         x = stem.forward(x)
         feats.append(x)
         # float bits of max |activation| per image, one row per layer output: raised by the producing kernel (atomicMax)
-        maxima = torch.zeros((1 + 2 * sum(len(b) for b in trunk), x.shape[0]), device=x.device, dtype=torch.int32)
+        per_block = len(self.block.convs)
+        maxima = torch.zeros((1 + per_block * sum(len(b) for b in trunk), x.shape[0]), device=x.device, dtype=torch.int32)
         xmax, row = maxima[0], 1
         x = ops.maxpool_nhwc(x, xmax)                                          # NHWC from here on
         for blocks in trunk:
-            for conv1, conv2, down in blocks:
+            for *convs, down in blocks:
+                # the projection without ReLU; ReLU after every convolution, the last one behind the residual
                 skip = x if down is None else down.forward(x, xmax, relu=False)
-                y = conv1.forward(x, xmax, ymax=maxima[row])
-                x = conv2.forward(y, maxima[row], residual=skip, ymax=maxima[row + 1])
-                xmax, row = maxima[row + 1], row + 2
+                y, ymax = x, xmax
+                for conv in convs[:-1]:
+                    y = conv.forward(y, ymax, ymax=maxima[row])
+                    ymax, row = maxima[row], row + 1
+                x = convs[-1].forward(y, ymax, residual=skip, ymax=maxima[row])
+                xmax, row = maxima[row], row + 1
             feats.append(ops.nhwc_to_nchw(x))
         return feats
 
@@ -190,6 +233,21 @@ class ResNet34(nn.Module):
 
     def forward(self, x, early_feat=True):
         return self.pyramid(x)[-1]
+
+
+class ResNet34(_ResNet):
+    """BasicBlock (3, 4, 6): 64 / 64 / 128 / 256 channels at levels 1..4, the released model (reference resnet.py:175-179)."""
+    block, stages = _Basic, _STAGES
+
+
+class ResNet50(_ResNet):
+    """Bottleneck blocks (3, 4, 6): 64 / 256 / 512 / 1024 channels at levels 1..4 (reference resnet.py:181-185)."""
+    block, stages = _Bottleneck, _STAGES
+
+
+class ResNet101(_ResNet):
+    """Bottleneck blocks (3, 4, 23): the backbone NCNet was published with (reference resnet.py:187-191)."""
+    block, stages = _Bottleneck, _STAGES101
 
 
 def pair_pyramids(extract, im1, im2, both=None):

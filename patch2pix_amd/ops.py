@@ -837,8 +837,8 @@ def regress_batch_dev(reg1, reg2, pyrs1, pyrs2, proposals, counts, want_raw=Fals
     proposals = proposals.contiguous()
     pyr_a, pyr_b, keep = (_lib.Pyramid * nb)(), (_lib.Pyramid * nb)(), []
     for i in range(nb):
-        pa, ka = _pyramid(pyrs1[i])
-        pb, kb = _pyramid(pyrs2[i])
+        pa, ka = _pyramid(pyrs1[i], reg1.layout["feat_idx"])
+        pb, kb = _pyramid(pyrs2[i], reg1.layout["feat_idx"])
         pyr_a[i], pyr_b[i] = pa, pb
         keep.append((ka, kb))
     given = out or {}
@@ -886,7 +886,9 @@ def _regress_scratch(dev, n, reg=None):
     return torch.empty(max(int(nbytes), 128), dtype=torch.uint8, device=dev)
 
 
-def _pyramid(levels):
+def _pyramid(levels, used=(0, 1, 2, 3)):
+    """used: the levels the regressor reads (its feat_idx).  Only those are held to the 3 / 64 / 64 / 128 channels the library
+    gathers; a level it never reads (levels 2, 3 of a Bottleneck pyramid under feat_idx within {0, 1}) travels as a pointer."""
     if len(levels) != 4:
         raise ValueError("a pyramid is the 4 maps of feat_idx [0,1,2,3]")
     lv = [_f32c(t, "pyramid level") for t in levels]
@@ -895,8 +897,8 @@ def _pyramid(levels):
         raise ValueError(f"images must be at least 8x8 pixels (got {h}x{w})")
     up = lambda d, j: (d + (1 << j) - 1) >> j          # the backbone's strided layers round up (resnet.py)
     exp = [(3, h, w), (64, up(h, 1), up(w, 1)), (64, up(h, 2), up(w, 2)), (128, up(h, 3), up(w, 3))]
-    for t, e in zip(lv, exp):
-        if tuple(t.shape) != e:
+    for j, (t, e) in enumerate(zip(lv, exp)):
+        if j in used and tuple(t.shape) != e:
             raise ValueError(f"pyramid level has shape {tuple(t.shape)}, expected {e}")
     p = _lib.Pyramid()
     for j in range(4):
@@ -931,8 +933,8 @@ def regress_batch(reg1, reg2, pyrs1, pyrs2, proposals, want_mid=True, want_raw=F
     pyr_b = (_lib.Pyramid * nitems)()
     keep = []
     for i in range(nitems):
-        pa, ka = _pyramid(pyrs1[i])
-        pb, kb = _pyramid(pyrs2[i])
+        pa, ka = _pyramid(pyrs1[i], reg1.layout["feat_idx"])
+        pb, kb = _pyramid(pyrs2[i], reg1.layout["feat_idx"])
         pyr_a[i], pyr_b[i] = pa, pb
         keep.append((ka, kb))
     cnt = (ctypes.c_int * nitems)(*counts)

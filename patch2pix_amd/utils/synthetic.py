@@ -224,6 +224,104 @@ def make_checkpoint(seed=0, regressor_config=None, feat_idx=None, **kw):
             "state_dict": make_state_dict(seed, **kw), "optim": None}
 
 
+def _named_backbone(gen, sd, backbone):
+    """`extract.*` tensors of a named backbone up to layer3 (networks/resnet.py): Xavier-uniform filters, every BatchNorm
+    randomised (`_bn`), the weight of a block's last BatchNorm halved (the residual stream of 33 blocks must stay in range)."""
+    from ..networks import resnet
+    cls = getattr(resnet, backbone)
+    last = cls.block.convs[-1][1]
+
+    def conv_bn(name_c, name_b, cout, cin, k):
+        sd[name_c + ".weight"] = _xavier(gen, cout, cin, k, k)
+        _bn(gen, sd, name_b, cout)
+
+    conv_bn("extract.conv1", "extract.bn1", 64, 3, 7)
+    cin = 64
+    for lname, planes, blocks, _ in cls.stages:
+        cout = planes * cls.block.expansion
+        for b in range(blocks):
+            p = f"extract.{lname}.{b}"
+            if cls.block.expansion == 1:
+                conv_bn(p + ".conv1", p + ".bn1", planes, cin, 3)
+                conv_bn(p + ".conv2", p + ".bn2", planes, planes, 3)
+            else:
+                conv_bn(p + ".conv1", p + ".bn1", planes, cin, 1)
+                conv_bn(p + ".conv2", p + ".bn2", planes, planes, 3)
+                conv_bn(p + ".conv3", p + ".bn3", cout, planes, 1)
+            sd[f"{p}.{last}.weight"] *= 0.5
+            if b == 0 and (cin != cout or lname != "layer1"):
+                conv_bn(p + ".downsample.0", p + ".downsample.1", cout, cin, 1)
+            cin = cout
+
+
+def backbone_contrast_shift(sd, backbone, change_stride, kappa=1.0, height=128, width=192):
+    """`contrast_shift` for a named backbone: the per-channel shift (rounded to 1/64) that leaves the layer-3 features of a
+    random-init backbone sparse -- mean + kappa * standard deviation of the last block's pre-ReLU output over one synthetic
+    image pair.  Runs the torch path on the CPU; fixtures store the shift they were made with."""
+    import torch.nn.functional as F
+    from ..networks import resnet
+    net = getattr(resnet, backbone)()
+    if change_stride:
+        net.change_stride("layer3")
+    net.load_state_dict({k[len("extract."):]: v for k, v in sd.items() if k.startswith("extract.")}, strict=False)
+    net.eval()
+    blk, cols = net.layer3[-1], []
+    with torch.no_grad():
+        for im in make_image_pair(900, height, width):
+            x = image_tensor(im)[None]
+            x = F.relu(net.bn1(net.conv1(x)))
+            x = net.layer2(net.layer1(F.max_pool2d(x, 3, 2, 1)))
+            for b in net.layer3[:-1]:
+                x = b(x)
+            y = x
+            for i, (c, bn) in enumerate(blk.convs):
+                y = getattr(blk, bn)(getattr(blk, c)(y))
+                if i + 1 < len(blk.convs):
+                    y = F.relu(y)
+            z = y + x
+            cols.append(z[0].reshape(z.shape[1], -1))
+    z = torch.cat(cols, dim=1)
+    return torch.round((z.mean(dim=1) + kappa * z.std(dim=1)) * 64) / 64
+
+
+def image_tensor(im):
+    """uint8 [H,W,3] -> float32 [3,H,W], /255 and ImageNet mean / std (utils/datasets/preprocess.py)."""
+    mean = torch.tensor([0.485, 0.456, 0.406]).view(3, 1, 1)
+    std = torch.tensor([0.229, 0.224, 0.225]).view(3, 1, 1)
+    return (torch.from_numpy(im).permute(2, 0, 1).float() / 255 - mean) / std
+
+
+def make_backbone_checkpoint(seed, backbone="ResNet50", change_stride=True, regressor_config=None, feat_idx=None, contrast=None,
+                             peaky_ncn=True):
+    """A seeded checkpoint in the reference's schema (utils/train/helper.py:10-20) for a named backbone and stride: the
+    backbone from `_named_backbone` (Xavier, randomised BatchNorm statistics), the consensus filters of `make_state_dict`,
+    and -- with a `regressor_config` (+ `feat_idx`) -- regressors of that configuration; without one the checkpoint is
+    NC-only ('regressor_config': None).  `contrast`: None, a float kappa (calibrate `backbone_contrast_shift` here) or the shift
+    tensor a fixture stores; it is subtracted from the bias of the last BatchNorm of layer3.  A generator of its own:
+    `make_state_dict` keeps its draws."""
+    from ..networks import resnet
+    gen = torch.Generator().manual_seed(int(seed))
+    sd = {}
+    _named_backbone(gen, sd, backbone)
+    if contrast is not None:
+        shift = (backbone_contrast_shift(sd, backbone, change_stride, float(contrast)) if isinstance(contrast, (int, float))
+                 else torch.as_tensor(contrast).float())
+        cls = getattr(resnet, backbone)
+        key = f"extract.layer3.{cls.stages[-1][2] - 1}.{cls.block.convs[-1][1]}.bias"
+        sd[key] = sd[key] - shift
+    _ncn(gen, sd, peaky_ncn)
+    fi = list(feat_idx) if feat_idx is not None else [0, 1, 2, 3]
+    if regressor_config is not None:
+        feat_dim = sum(_FEAT_DIMS[i] for i in fi)
+        _regressor(gen, sd, "regress_mid", feat_dim, regressor_config)
+        if getattr(regressor_config, "shared", False):
+            sd.update({"regress_fine." + k[len("regress_mid."):]: v for k, v in list(sd.items()) if k.startswith("regress_mid.")})
+        else:
+            _regressor(gen, sd, "regress_fine", feat_dim, regressor_config)
+    return {"last_epoch": 0, "best_vals": None, "backbone": backbone, "feat_idx": fi, "change_stride": bool(change_stride),
+            "regressor_config": regressor_config, "state_dict": sd, "optim": None}
+
+
 def make_pyramid(seed, height, width, device="cpu"):
     """Synthetic post-ReLU-like feature pyramid of one image, shapes as reference
     resnet.py:138-157 with change_stride: [3,H,W],[64,H/2,W/2],[64,H/4,W/4],[128,H/8,W/8],[256,H/8,W/8]."""
