@@ -184,10 +184,23 @@ typedef struct p2p_regressor_tensors {
     const float *out_w, *out_b;
 } p2p_regressor_tensors;
 int p2p_regressor_create_config(const p2p_regressor_config *config, const p2p_regressor_tensors *tensors, p2p_regressor **out);
-/* The mode id of a generic handle: p2p_regressor_get_mode returns it, p2p_regressor_set_mode accepts only it on a generic
- * handle and refuses it on a tuned one (P2P_EUNSUPPORTED both ways).  In p2p_regress* reg1 and reg2 must be of the same kind,
- * and two generic handles must have equal configurations (P2P_EINVAL otherwise).                                      */
+/* The mode ids of a generic handle.  New generic handles start in P2P_REGRESS_GENERIC (exact fp32, above).
+ *   P2P_REGRESS_GENERIC_FP16X2 (opt-in, fp32-equivalent) runs the convolution stack on v_mfma_f32_32x32x16_f16 with the scheme of
+ *     P2P_REGRESS_FP16X2: every fp32 operand, scaled by an exact power of two, as two fp16 planes, three MFMA products per
+ *     fp32 product (a0 b0 + a0 b1 + a1 b0), fp32 accumulation.  Weights carry a per-output-channel exponent folded into the
+ *     BatchNorm scale; layer 0 reads the L2-normalised patches under the fixed scale 2^12; an inner layer reads its input
+ *     under a per-SAMPLE power of two derived from the largest magnitude the producing layer stored for that sample.  The
+ *     gather, the FC tail and the final Linear are those of P2P_REGRESS_GENERIC.  Outputs stay a function of the proposal and
+ *     the configuration alone (bit-identical alone, in any batch, with device-side counts, under any chunk size), but they
+ *     are NOT the bits of P2P_REGRESS_GENERIC; both modes are held to the same bars.
+ * p2p_regressor_set_mode on a generic handle accepts these two ids (the first selection of P2P_REGRESS_GENERIC_FP16X2 packs
+ * and uploads its weight planes; going back to P2P_REGRESS_GENERIC gives the handle's earlier outputs bit for bit), answers
+ * P2P_EUNSUPPORTED for the ids of the tuned modes and P2P_EINVAL for an id the library does not know.  A tuned handle
+ * refuses both generic ids (P2P_EUNSUPPORTED).  p2p_regressor_get_mode returns the current id.  In p2p_regress* reg1 and
+ * reg2 must be of the same kind, two generic handles must have equal configurations and be in the same mode (P2P_EINVAL
+ * otherwise; the message names both modes).                                                                          */
 #define P2P_REGRESS_GENERIC 16
+#define P2P_REGRESS_GENERIC_FP16X2 17
 
 /* ---- coarse stage ---------------------------------------------------------------------------- */
 
@@ -480,7 +493,9 @@ size_t p2p_regress_workspace_bytes_mode(int n, int mode);
  *   4 (mid matches) + fc_in (pooled features) + 2 max(fc_dim) + the largest activation a layer reads + the largest it writes
  * floats, activations counted as spp x h x w x channels (spp = 2 samples per proposal for 'post', 1 for 'pre'; layer 0
  * reads 16 x 16 x the selected channels padded to a multiple of 8).  Released configuration: 669 712 bytes per proposal,
- * 171 MB at the cap of 256.  p2p_regress* derive their chunk from the workspace_bytes they are given -- the largest
+ * 171 MB at the cap of 256.  The value depends on the handle's mode: P2P_REGRESS_GENERIC_FP16X2 adds spp x (n_conv - 1)
+ * floats per proposal, the per-sample words its inner layers derive their input scales from (released configuration: 4
+ * bytes per proposal more) -- query again after p2p_regressor_set_mode.  p2p_regress* derive their chunk from the workspace_bytes they are given -- the largest
  * multiple of 8 proposals that fits, at most the cap -- and return P2P_ENOMEM below one unit of 8; results do not depend
  * on the chunk.                                                                                                     */
 size_t p2p_regress_workspace_bytes_for(const p2p_regressor *reg, int n);

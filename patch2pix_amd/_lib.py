@@ -203,7 +203,10 @@ p2p_regressor_get_mode = _sig("p2p_regressor_get_mode", ctypes.c_int, [ctypes.c_
 REGRESS_MODES = {"f32": 0, "fp16x2": 3, "fp16x2w": 4}      # the fp32-equivalent modes
 REGRESS_MODES_LOSSY = {"fp16": 5}     # P2P_REGRESS_FP16: opt-in, one fp16 plane per operand (not fp32-equivalent; kept apart from
                                       # the dict above, whose modes share the accuracy bars and the two-plane buffer layouts)
-REGRESS_GENERIC = 16          # P2P_REGRESS_GENERIC: the mode id of a handle made by p2p_regressor_create_config
+REGRESS_GENERIC = 16          # P2P_REGRESS_GENERIC: the mode id a handle made by p2p_regressor_create_config starts in
+# the modes of a generic handle, both fp32-equivalent: exact fp32 MFMA, and P2P_REGRESS_GENERIC_FP16X2 (the convolution stack
+# on two fp16 planes per operand, three MFMA products per product)
+REGRESS_MODES_GENERIC = {"generic": 16, "generic_fp16x2": 17}
 FEAT_COMB = {"pre": 0, "post": 1}
 
 EXPORTS = ["p2p_version", "p2p_last_error", "p2p_ncn_create", "p2p_ncn_destroy", "p2p_ncn_set_tile", "p2p_regressor_create",

@@ -116,6 +116,33 @@ static inline void pack_fc_mfma(const float *w, int n, int k, float *out) {
                     out[(((size_t)S * (n / 16) + t) * 64 + lane) * 4 + j] = w[(size_t)(16 * t + (lane & 15)) * k + 16 * S + 4 * (lane >> 4) + j];
 }
 
+// conv weight [co][cin][taps] (torch Conv2d, taps = k * k) -> the two-plane fp16 B fragments of v_mfma_f32_32x32x16_f16 in the
+// order regress_generic_h2.hip streams them, K in slabs of 16 input channels, slabs outer:
+//   out[((((slab * taps + tap) * ntiles + t) * 2 + plane) * 64 + lane) * 8 + i] = plane (0 high, 1 low) of
+//   W[n = 32 t + (lane & 31)][16 slab + 8 (lane >> 5) + i][tap] * 2^texp[n],      texp[n] = pow2_exponent_to(max |W[n]|, 12),
+// zeros past co and past cin (the last slab of a cin that is no multiple of 16).  conv_planes_halfs: fp16 values of the stream.
+static inline size_t conv_planes_halfs(int cin, int taps, int ntiles) { return (size_t)((cin + 15) / 16) * taps * ntiles * 1024; }
+static inline void pack_conv_planes(const float *w, int co, int cin, int taps, int ntiles, uint16_t *out, int *texp) {
+    const int nslab = (cin + 15) / 16;
+    for (int n = 0; n < co; ++n) {
+        double mx = 0.0;
+        for (size_t q = 0; q < (size_t)cin * taps; ++q) mx = std::max(mx, (double)std::fabs(w[(size_t)n * cin * taps + q]));
+        texp[n] = pow2_exponent_to(mx, 12);
+    }
+    for (int sl = 0; sl < nslab; ++sl)
+        for (int tap = 0; tap < taps; ++tap)
+            for (int t = 0; t < ntiles; ++t)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int i = 0; i < 8; ++i) {
+                        const int n = 32 * t + (lane & 31), chn = 16 * sl + 8 * (lane >> 5) + i;
+                        uint16_t hi = 0, lo = 0;
+                        if (n < co && chn < cin) split_fp16_planes(std::ldexp(w[((size_t)n * cin + chn) * taps + tap], texp[n]), &hi, &lo);
+                        const size_t at = ((((size_t)sl * taps + tap) * ntiles + t) * 2 * 64 + lane) * 8 + i;
+                        out[at] = hi;
+                        out[at + 512] = lo;
+                    }
+}
+
 // ---- launchers ------------------------------------------------------------------------------------------------------------
 // What a launcher does before a kernel whose dynamic LDS allocation exceeds the default limit: ask for the current device (once
 // per launch) and, on that device's first launch, raise the limit of each kernel; `once` is set only after all of them succeeded.

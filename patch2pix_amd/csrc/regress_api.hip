@@ -4,6 +4,7 @@
 // as part of api.hip, not as a unit of its own.
 #include "regress_common.h"
 #include "regress_generic.hip"      // the shape-generic kernels and their handle (generic regressors; no unit of its own either)
+#include "regress_generic_h2.hip"   // their fp16x2 convolution stack (mode P2P_REGRESS_GENERIC_FP16X2)
 
 using namespace p2p;
 
@@ -88,13 +89,25 @@ static int ensure_mode(p2p_regressor *r, int mode) {
 
 extern "C" int p2p_regressor_set_mode(p2p_regressor *reg, int mode) {
     P2P_REQUIRE(reg, P2P_EINVAL, "p2p_regressor_set_mode: null handle");
+    const bool generic_id = mode == P2P_REGRESS_GENERIC || mode == P2P_REGRESS_GENERIC_FP16X2;
     if (reg->gen) {
-        P2P_REQUIRE(mode == P2P_REGRESS_GENERIC, P2P_EUNSUPPORTED,
-                    "p2p_regressor_set_mode: a generic regressor (p2p_regressor_create_config) runs P2P_REGRESS_GENERIC only");
+        P2P_REQUIRE(generic_id || mode_index(mode) >= 0, P2P_EINVAL, "p2p_regressor_set_mode: unknown mode %d", mode);
+        P2P_REQUIRE(generic_id, P2P_EUNSUPPORTED,
+                    "p2p_regressor_set_mode: a generic regressor (p2p_regressor_create_config) runs P2P_REGRESS_GENERIC or "
+                    "P2P_REGRESS_GENERIC_FP16X2, not the tuned mode %d", mode);
+        if (mode == P2P_REGRESS_GENERIC_FP16X2) {       // the planes are allocated on the HANDLE's device
+            int cur = 0;
+            P2P_HIP_CHECK(hipGetDevice(&cur));
+            if (cur != reg->device) P2P_HIP_CHECK(hipSetDevice(reg->device));
+            const int st = regressor_generic_ensure_h2(reg->gen);
+            if (cur != reg->device) P2P_HIP_CHECK(hipSetDevice(cur));
+            if (st != P2P_OK) return st;
+        }
+        reg->mode = reg->gen->mode = mode;
         return P2P_OK;
     }
-    P2P_REQUIRE(mode != P2P_REGRESS_GENERIC, P2P_EUNSUPPORTED,
-                "p2p_regressor_set_mode: P2P_REGRESS_GENERIC needs a handle made by p2p_regressor_create_config");
+    P2P_REQUIRE(!generic_id, P2P_EUNSUPPORTED,
+                "p2p_regressor_set_mode: mode %d needs a handle made by p2p_regressor_create_config", mode);
     P2P_REQUIRE(mode_index(mode) >= 0, P2P_EINVAL, "p2p_regressor_set_mode: unknown mode %d", mode);
     // the weight stream of a mode is allocated on the HANDLE's device, whatever the caller's current device is
     int cur = 0;
@@ -206,7 +219,8 @@ static int regress_batch_impl(const p2p_regressor *reg1, const p2p_regressor *re
     P2P_REQUIRE(!reg2 || !reg2->gen == !reg1->gen, P2P_EINVAL, "p2p_regress: a generic and a tuned regressor cannot be chained");
     P2P_REQUIRE(!reg2 || !reg1->gen || memcmp(&reg1->gen->cfg, &reg2->gen->cfg, sizeof(p2p_regressor_config)) == 0, P2P_EINVAL,
                 "p2p_regress: the two generic regressors have different configurations");
-    P2P_REQUIRE(!reg2 || reg2->mode == reg1->mode, P2P_EINVAL, "p2p_regress: the two regressors use different arithmetic modes");
+    P2P_REQUIRE(!reg2 || reg2->mode == reg1->mode, P2P_EINVAL, "p2p_regress: the two regressors use different arithmetic modes (%d and %d)",
+                reg1->mode, reg2->mode);
     for (int i = 0; i < nitems; ++i) {
         const p2p_pyramid *im[2] = {im1 + i, im2 + i};
         for (int s = 0; s < 2; ++s) {
@@ -224,7 +238,7 @@ static int regress_batch_impl(const p2p_regressor *reg1, const p2p_regressor *re
         most = std::max(most, n);
     }
     // a generic regressor needs one unit of 8 proposals at least and cuts its chunk to what it is given
-    const size_t need = reg1->gen ? reg1->gen->per_prop * GEN_UNIT * sizeof(float) : MODES[m].ws_floats((size_t)most) * sizeof(float);
+    const size_t need = reg1->gen ? gen_per_prop(*reg1->gen) * GEN_UNIT * sizeof(float) : MODES[m].ws_floats((size_t)most) * sizeof(float);
     if (need) {
         P2P_REQUIRE(workspace && ((uintptr_t)workspace & 127) == 0, P2P_EINVAL,
                     "p2p_regress: a 128-byte aligned workspace of %zu bytes (p2p_regress_workspace_bytes_mode) is needed", need);
@@ -297,7 +311,7 @@ extern "C" size_t p2p_regress_workspace_bytes_for(const p2p_regressor *reg, int 
     if (!reg || n <= 0) return 0;
     if (!reg->gen) return p2p_regress_workspace_bytes_mode(n, reg->mode);
     const size_t units = ((size_t)std::min(n, GEN_CAP) + GEN_UNIT - 1) / GEN_UNIT;
-    return units * GEN_UNIT * reg->gen->per_prop * sizeof(float);
+    return units * GEN_UNIT * gen_per_prop(*reg->gen) * sizeof(float);      // by the handle's mode
 }
 
 extern "C" int p2p_regress_batch_dev(const p2p_regressor *reg1, const p2p_regressor *reg2, int nitems,

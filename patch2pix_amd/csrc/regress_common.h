@@ -424,6 +424,19 @@ struct GenNet {                          // one regressor as its kernels see it
     const float *out_w, *out_b;          // final Linear [5][k_out], [5]
     int k_out;
 };
+// ---- regress_generic_h2.hip: the convolution stack of mode P2P_REGRESS_GENERIC_FP16X2 (two fp16 planes per operand, three
+// v_mfma_f32_32x32x16_f16 per product).  K runs in slabs of 16 input channels, slabs outer, taps inner; a work-group stages
+// the slab of every sample its rows touch into LDS -- split into the planes there -- and reads the taps from LDS.
+constexpr int GEN_H2_PIX = 80;           // bytes of a staged pixel: 16 high halves | 16 low halves | 16 bytes of padding = 5
+                                         // 16-byte slots, an ODD stride (NOTES.md: conflict-free A-fragment reads)
+constexpr int GEN_H2_HEAD = 1024;        // in front of the pixels: 2^e and 2^-e of each staged sample (at most 128)
+constexpr int GEN_H2_FLUSH = 8;          // slabs per accumulator chain: the MFMA accumulators are added into a second set
+                                         // (VALU fp32) and restart from zero, like corr_pool_kernel<WIDE>
+struct GenConvH2 {                       // what a layer's kernel reads beside its GenConv
+    const unsigned char *w;              // pack_conv_planes (host_pack.h) + one (tap) step of zeros the prefetch runs into
+    const float *scale;                  // [co] BatchNorm scale x 2^-texp[n]
+    int nslab, wrows, lds_bytes;         // wrows: 32-row tiles of a work-group (4, 2 or 1; the other waves take further columns)
+};
 struct GenReg {
     p2p_regressor_config cfg;            // normalised: entries past n_feat / n_conv / n_fc are zero
     GenNet net;
@@ -431,7 +444,17 @@ struct GenReg {
     // workspace of a chunk of U proposals (floats per proposal): mid matches 4, V fc_in, two FC buffers fc_max each, the
     // activation buffers a layer reads (act_a: even layers' input) and writes (act_b) -- offsets are these times U
     size_t fc_max, act_a, act_b, per_prop;
+    // P2P_REGRESS_GENERIC_FP16X2: the mode (mirrors p2p_regressor::mode), its blob (packed on the first selection from the
+    // host copies below), its view, and what it appends to a chunk's workspace: amax_pp = spp x (n_conv - 1) words per
+    // proposal, [layer boundary][sample], the float bits of the largest |value| a layer stored for the sample
+    int mode = P2P_REGRESS_GENERIC;
+    DeviceBlob mem_h2;
+    GenConvH2 h2[GEN_MAX_LAYERS] = {};
+    size_t amax_pp = 0;
+    int cin[GEN_MAX_LAYERS] = {};        // real input channels of a layer (GenConv::ci is padded)
+    std::vector<float> conv_w_host[GEN_MAX_LAYERS], scale_host[GEN_MAX_LAYERS];
 };
+static inline size_t gen_per_prop(const GenReg &g) { return g.per_prop + (g.mode == P2P_REGRESS_GENERIC_FP16X2 ? g.amax_pp : 0); }
 // the parts of a chunk's workspace, in floats from its start (U proposals, a multiple of GEN_UNIT)
 static inline size_t gen_ws_mid(const GenReg &, size_t) { return 0; }
 static inline size_t gen_ws_v(const GenReg &, size_t U) { return 4 * U; }
@@ -439,7 +462,10 @@ static inline size_t gen_ws_fc(const GenReg &g, size_t U, int which) { return (4
 static inline size_t gen_ws_act(const GenReg &g, size_t U, int which) {
     return (4 + g.net.fc_in + 2 * g.fc_max + (which ? g.net.spp * g.act_a : 0)) * U;
 }
+static inline size_t gen_ws_amax(const GenReg &g, size_t U) { return g.per_prop * U; }      // behind everything else
 int regressor_generic_create(const p2p_regressor_config *cfg, const p2p_regressor_tensors *t, GenReg **out);
+// pack + upload the weight planes of P2P_REGRESS_GENERIC_FP16X2 (once per handle; P2P_ENOMEM / P2P_EHIP leave the handle as it was)
+int regressor_generic_ensure_h2(GenReg *g);
 // slots [0, n) of the launch described by `a` through reg1 (and reg2 on its un-truncated output when given), chunk by chunk
 int launch_regress_generic(const GenReg &reg1, const GenReg *reg2, const RegressArgs &a, int n, size_t workspace_bytes,
                            hipStream_t stream);
@@ -461,13 +487,14 @@ __device__ __forceinline__ float regress_parse_one(float s, int o, float base, c
 constexpr int P2P_REGRESS_NMODES = 4;
 struct p2p_regressor {
     int device = 0;    // the device the handle was created on: every later allocation (another mode's weight stream) goes there
-    int mode = 0;      // P2P_REGRESS_F32 | P2P_REGRESS_FP16X2 | P2P_REGRESS_FP16X2W | P2P_REGRESS_FP16 (tuned handles), P2P_REGRESS_GENERIC (generic ones)
+    int mode = 0;      // P2P_REGRESS_F32 | P2P_REGRESS_FP16X2 | P2P_REGRESS_FP16X2W | P2P_REGRESS_FP16 (tuned handles),
+                       // P2P_REGRESS_GENERIC | P2P_REGRESS_GENERIC_FP16X2 (generic ones; GenReg::mode holds the same value)
     p2p::DeviceBlob dev;                            // BatchNorm folds + FC layers (every mode)
     p2p::DeviceBlob stream[P2P_REGRESS_NMODES];     // a mode's convolution weights in its kernels' stream order (+ the BatchNorm scales with
                                                     // its exponents folded in); packed and uploaded on the mode's first selection
     std::vector<float> conv1_w, conv2_w, bn1s_host, bn2s_host;   // host copies the packings are built from
     p2p::RegDev common{}, view[P2P_REGRESS_NMODES]{};
-    p2p::GenReg *gen = nullptr;      // a generic handle (p2p_regressor_create_config; mode P2P_REGRESS_GENERIC): everything above but
+    p2p::GenReg *gen = nullptr;      // a generic handle (p2p_regressor_create_config; the two generic modes): everything above but
                                      // `device` and `mode` is unused; null for a tuned handle
     ~p2p_regressor() { delete gen; }
 };

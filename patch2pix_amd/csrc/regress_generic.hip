@@ -2,7 +2,8 @@
 // (p2p_regressor_config), exact fp32 on the matrix cores.  The tuned kernels (regress.hip, regress_h2.hip, regress_wino.hip) are
 // built around 518 / 512 channels and the 8x8 map; this file trades their fusion for generality: a chunk of proposals goes
 // through the network layer by layer, one launch per layer, activations in the caller's workspace (layout: regress_common.h).
-// The handle (GenReg) holds every packed weight, fold and bias in one DeviceBlob (host_pack.h).
+// The handle (GenReg) holds every packed weight, fold and bias in one DeviceBlob (host_pack.h).  The opt-in second arithmetic of a
+// generic handle (P2P_REGRESS_GENERIC_FP16X2) replaces gen_conv_kernel alone: regress_generic_h2.hip, chosen in gen_run_level.
 // Device code is restricted to what the kernel emulator of the test-suite runs: the two fp32 MFMA shapes, __shfl_xor,
 // atomicMax on int.  Compiled as part of api.hip (through regress_api.hip), not as a unit of its own.
 #include "regress_common.h"
@@ -361,8 +362,13 @@ int regressor_generic_create(const p2p_regressor_config *cfg, const p2p_regresso
         const GenConv &L = N.conv[i];
         gen_pack_conv(t->conv_w[i], L.co, cin, L.ci, L.ker, L.ntiles, &h[o_cw[i]]);
         fold_bn(t->conv_bn[i], L.co, &h[o_cs[i]], &h[o_cb[i]]);
+        // host copies: the planes of P2P_REGRESS_GENERIC_FP16X2 are packed from them on that mode's first selection
+        g->cin[i] = cin;
+        g->conv_w_host[i].assign(t->conv_w[i], t->conv_w[i] + (size_t)L.co * cin * L.ker * L.ker);
+        g->scale_host[i].assign(&h[o_cs[i]], &h[o_cs[i]] + L.co);
         cin = L.co;
     }
+    g->amax_pp = (size_t)N.spp * (cfg->n_conv - 1);
     for (int i = 0; i < cfg->n_fc; ++i) {
         const GenFc &L = N.fc[i];
         pack_fc_mfma(t->fc_w[i], L.n, L.k, &h[o_fw[i]]);
@@ -389,7 +395,13 @@ int regressor_generic_create(const p2p_regressor_config *cfg, const p2p_regresso
     return P2P_OK;
 }
 
-// one level of one chunk: gather, the conv stack, the FC tail, the outputs
+// regress_generic_h2.hip: one convolution layer of mode P2P_REGRESS_GENERIC_FP16X2 over the chunk.  amax_in: the per-sample words
+// the layer derives its input scales from (null: layer 0, fixed scale), amax_out: the words its stores are reduced into (null:
+// the last layer)
+int launch_gen_conv_h2(const RegressArgs &a, const GenChunk &ch, const GenConvArgs &c, const GenConvH2 &H, const int *amax_in,
+                       int *amax_out, hipStream_t stream);
+
+// one level of one chunk: gather, the conv stack (by the handle's mode), the FC tail, the outputs
 static int gen_run_level(const GenReg &R, const RegressArgs &a, const GenChunk &ch, float *ws, size_t U, bool more,
                          hipStream_t stream) {
     const GenNet &N = R.net;
@@ -402,11 +414,20 @@ static int gen_run_level(const GenReg &R, const RegressArgs &a, const GenChunk &
     int st = check_launch("gen_gather_kernel");
     if (st != P2P_OK) return st;
     P2P_HIP_CHECK(hipMemsetAsync(V, 0, (size_t)ch.cnt * N.fc_in * sizeof(float), stream));
+    const bool h2 = R.mode == P2P_REGRESS_GENERIC_FP16X2;
+    int *amax = h2 ? (int *)(ws + gen_ws_amax(R, U)) : nullptr;      // [layer boundary][sample] (that mode's part of the workspace)
+    const size_t nsamp = (size_t)ch.cnt * N.spp;
+    if (h2 && N.n_conv > 1) P2P_HIP_CHECK(hipMemsetAsync(amax, 0, (N.n_conv - 1) * nsamp * sizeof(int), stream));
     for (int i = 0; i < N.n_conv; ++i) {
         GenConvArgs c;
         c.in = act[i & 1]; c.L = N.conv[i]; c.spp = N.spp; c.last = i + 1 == N.n_conv;
         c.out = c.last ? V : act[(i + 1) & 1];
         c.rows = ch.cnt * N.spp * c.L.ho * c.L.wo;
+        if (h2) {
+            st = launch_gen_conv_h2(a, ch, c, R.h2[i], i ? amax + (i - 1) * nsamp : nullptr, c.last ? nullptr : amax + i * nsamp, stream);
+            if (st != P2P_OK) return st;
+            continue;
+        }
         hipLaunchKernelGGL(gen_conv_kernel, dim3(ceil_div(c.rows, GEN_ROWS), c.L.ntiles / 2), dim3(256), 0, stream, a, ch, c);
         st = check_launch("gen_conv_kernel");
         if (st != P2P_OK) return st;
@@ -429,7 +450,7 @@ static int gen_run_level(const GenReg &R, const RegressArgs &a, const GenChunk &
 int launch_regress_generic(const GenReg &reg1, const GenReg *reg2, const RegressArgs &a, int n, size_t workspace_bytes,
                            hipStream_t stream) {
     // the chunk: the largest multiple of GEN_UNIT proposals whose scratch fits (the caller checked that one unit does)
-    const size_t unit_bytes = reg1.per_prop * GEN_UNIT * sizeof(float);
+    const size_t unit_bytes = gen_per_prop(reg1) * GEN_UNIT * sizeof(float);
     size_t U = std::min<size_t>(workspace_bytes / unit_bytes, GEN_CAP / GEN_UNIT) * GEN_UNIT;
     U = std::min(U, ((size_t)n + GEN_UNIT - 1) / GEN_UNIT * GEN_UNIT);
     for (int p0 = 0; p0 < n; p0 += (int)U) {

@@ -7,6 +7,8 @@ backbone (networks/resnet.py) keeps its torch parameters and runs its convolutio
 library; everything after the feature pyramid is HIP as well.  Inference only:
 `config.training=True` raises (training is out of scope).
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -199,6 +201,9 @@ class Patch2Pix(nn.Module):
                 mid = ops.RegressorWeights(sub("regress_mid."), self.device, self.regressor_config, self.feat_idx)
                 fine = mid if self.shared else ops.RegressorWeights(sub("regress_fine."), self.device,
                                                                     self.regressor_config, self.feat_idx)
+                if getattr(self, "_fine_mode", None) is not None:     # the new handles start in their default mode
+                    for reg in {id(mid): mid, id(fine): fine}.values():
+                        reg.set_mode(self._fine_mode)
             self._packed = (ncn, mid, fine)
         return self._packed
 
@@ -221,6 +226,46 @@ class Patch2Pix(nn.Module):
         if self._ncn_layout != ops.RELEASED_NCN_LAYOUT:
             return "fp16x2"
         return getattr(self, "_coarse_mode", None) or ops.default_coarse_mode()
+
+    def _fine_mode_names(self):
+        """The mode names the packed regressors of this model accept: the generic ones for a generic regressor, the tuned ones
+        for the released configuration."""
+        if self._layout != ops.RELEASED_LAYOUT:
+            return dict(ops._lib.REGRESS_MODES_GENERIC)
+        return {**ops._lib.REGRESS_MODES, **ops._lib.REGRESS_MODES_LOSSY}
+
+    def set_fine_mode(self, mode):
+        """The arithmetic of the fine stage's convolutions (ops.RegressorWeights.set_mode).  A model with generic regressors (any
+        configuration but the released one) accepts 'generic' (default, exact fp32 MFMA) and the opt-in 'generic_fp16x2' (two fp16
+        planes per operand, three MFMA products, fp32-equivalent); a model with the released configuration accepts the tuned names
+        ('fp16x2w', 'fp16x2', 'f32', the opt-in lossy 'fp16').  A name of the other kind raises NotImplementedError, an unknown one
+        ValueError, a model without regressors ValueError -- all before anything changes.  The choice belongs to the model: it is
+        applied to both packed handles now and again whenever the weights are re-packed (load_state_dict, init_weights_)."""
+        if self.regress_mid is None:
+            raise ValueError("set_fine_mode: this model has no regressors")
+        known = {**ops._lib.REGRESS_MODES, **ops._lib.REGRESS_MODES_LOSSY, **ops._lib.REGRESS_MODES_GENERIC}
+        if mode not in known:
+            raise ValueError(f"unknown fine mode {mode!r}: one of {sorted(self._fine_mode_names())}")
+        if mode not in self._fine_mode_names():
+            raise NotImplementedError(f"set_fine_mode: {mode!r} is no mode of this model's regressors "
+                                      f"(one of {sorted(self._fine_mode_names())})")
+        self._fine_mode = mode
+        if self._packed is not None:
+            for reg in {id(r): r for r in self._packed[1:]}.values():
+                reg.set_mode(mode)
+
+    @property
+    def fine_mode(self):
+        """The mode `set_fine_mode` chose, or the one new handles start in (P2P_REGRESS_GENERIC_MODE, else 'generic', for generic
+        regressors; P2P_REGRESS_MODE, else 'fp16x2w', for the released configuration); None for a model without regressors."""
+        if self.regress_mid is None:
+            return None
+        chosen = getattr(self, "_fine_mode", None)
+        if chosen is not None:
+            return chosen
+        if self._layout != ops.RELEASED_LAYOUT:
+            return os.environ.get("P2P_REGRESS_GENERIC_MODE") or "generic"
+        return os.environ.get("P2P_REGRESS_MODE") or "fp16x2w"
 
     # ------------------------------------------------------------------ coarse stage
     def forward_coarse_match(self, feat1, feat2, ksize=1):

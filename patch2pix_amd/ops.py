@@ -393,8 +393,8 @@ class RegressorWeights:
     """Device-resident packed FeatRegressNet (reference networks/modules.py:56-112).
     `sd` maps the sub-state_dict keys ('conv.0.weight', 'fc.6.bias', ...) to tensors.  `config` / `feat_idx`: the
     checkpoint's `regressor_config` / `feat_idx` (None = the released ones).  The released configuration runs the tuned
-    kernels; every other one -- or `generic=True` -- a generic handle (p2p_regressor_create_config: exact fp32 MFMA, one
-    launch per layer)."""
+    kernels; every other one -- or `generic=True` -- a generic handle (p2p_regressor_create_config: one launch per layer; exact
+    fp32 MFMA by default, `set_mode("generic_fp16x2")` or P2P_REGRESS_GENERIC_MODE for the fp16x2 convolution stack)."""
 
     def __init__(self, sd, device, config=None, feat_idx=None, generic=False):
         lay = regressor_layout(config, feat_idx)
@@ -460,6 +460,9 @@ class RegressorWeights:
         with torch.cuda.device(self.device):
             _lib.check(_lib.p2p_regressor_create_config(ctypes.byref(c), ctypes.byref(t), ctypes.byref(self.handle)),
                        "p2p_regressor_create_config")
+        env = os.environ.get("P2P_REGRESS_GENERIC_MODE")      # tools: the mode new GENERIC handles start in (read here, not in the library)
+        if env:
+            self.set_mode(env)
 
     def set_mode(self, mode):
         """'fp16x2w' (default: fp32-equivalent, two fp16 planes under exact power-of-two scales, 3 MFMA products, the second
@@ -468,11 +471,20 @@ class RegressorWeights:
         operand and one MFMA product: relative operand rounding 2^-11, NOT held to the 1e-3 px / 1e-5 bars of the others;
         DESIGN.md section 4, "Single-plane mode").  The first selection of a
         non-default mode packs and uploads that mode's weight stream (host work, ~1 s)."""
-        if self.generic:
-            if mode == "generic":
-                return
-            raise NotImplementedError(f"regressor mode {mode!r}: a generic regressor runs the exact-fp32 generic kernels only")
         modes = {**_lib.REGRESS_MODES, **_lib.REGRESS_MODES_LOSSY}
+        if self.generic:
+            # 'generic' (default: exact fp32 MFMA) or the opt-in 'generic_fp16x2' (the convolution stack on two fp16 planes per
+            # operand, three MFMA products, fp32-equivalent: DESIGN.md section 4, "The generic regressor"); the first selection of
+            # the latter packs and uploads its weight planes, going back gives the earlier outputs bit for bit
+            if mode in modes:
+                raise NotImplementedError(f"regressor mode {mode!r}: a generic regressor runs one of {sorted(_lib.REGRESS_MODES_GENERIC)}")
+            if mode not in _lib.REGRESS_MODES_GENERIC:
+                raise ValueError(f"unknown regressor mode {mode!r}: one of {sorted(_lib.REGRESS_MODES_GENERIC)} for a generic regressor")
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.p2p_regressor_set_mode(self.handle, _lib.REGRESS_MODES_GENERIC[mode]), "p2p_regressor_set_mode")
+            return
+        if mode in _lib.REGRESS_MODES_GENERIC:
+            raise NotImplementedError(f"regressor mode {mode!r} needs a generic regressor (a non-released configuration, or generic=True)")
         if mode not in modes:
             removed = {"bf16x2": "round 5", "bf16x3": "round 4"}
             why = f" ({mode!r} was removed in {removed[mode]})" if mode in removed else ""
@@ -484,8 +496,8 @@ class RegressorWeights:
     @property
     def mode(self):
         code = _lib.p2p_regressor_get_mode(self.handle)
-        names = {v: k for k, v in {**_lib.REGRESS_MODES, **_lib.REGRESS_MODES_LOSSY}.items()}
-        return "generic" if code == _lib.REGRESS_GENERIC else names[code]
+        names = {v: k for k, v in {**_lib.REGRESS_MODES, **_lib.REGRESS_MODES_LOSSY, **_lib.REGRESS_MODES_GENERIC}.items()}
+        return names[code]
 
     def __del__(self):
         if getattr(self, "handle", None) and _lib is not None:

@@ -1,9 +1,12 @@
-"""Time the generic regressor (csrc/regress_generic.hip) beside the tuned exact-fp32 mode: one regress_batch call of
-NPROP proposals (default 6400) x 2 levels on one 480x640 pair --
-  * the released configuration (case R of tests/regressor_reference.py) through a generic handle and through the untouched
-    tuned `f32` mode, alternating in the same process (the yardstick), with the largest coordinate / score difference of the two;
-  * cases A and C (lighter configurations) through their generic handles.
-HIP events around the call, WARMUP calls first (default 2), the median and minimum of NITER timed calls (default 7).
+"""Time the generic regressor (csrc/regress_generic.hip, csrc/regress_generic_h2.hip) in both of its arithmetics beside the tuned
+modes: one regress_batch call of NPROP proposals (default 6400) x 2 levels on one 480x640 pair --
+  * the released configuration (case R of tests/regressor_reference.py) through the untouched tuned `f32` and `fp16x2` modes and
+    through a generic handle in `generic` (exact fp32 MFMA) and `generic_fp16x2` (two fp16 planes, three MFMA products), the four
+    alternating in the same process (one box, one call: the spread of each is known from the same run), with the largest
+    coordinate / score difference of generic against tuned f32 and of the two generic modes;
+  * cases A and C (lighter configurations) and the ResNet50 feat_idx [0, 1] configuration (tests/bottleneck_reference.py:
+    conv 64 / 64, fc 64 / 32 on 3 + 64 channels per image) in both generic modes.
+HIP events around the call, WARMUP rounds first (default 2), the median, minimum and maximum of NITER timed calls (default 7).
 Prints one line per measurement and, with --out FILE, writes them to FILE as well.  No GPU: fails."""
 import os
 import sys
@@ -49,11 +52,14 @@ def main():
         print(text, flush=True)
         lines.append(text)
 
-    def handles(case, generic):
-        ck = rr.checkpoint(case)
+    def handles(case, generic, mode=None, ck=None):
+        ck = ck or rr.checkpoint(case)
         kw = dict(config=ck["regressor_config"], feat_idx=ck["feat_idx"], generic=generic)
         mid = ops.RegressorWeights(rr.sub_params(ck["state_dict"], "regress_mid."), dev, **kw)
         fine = ops.RegressorWeights(rr.sub_params(ck["state_dict"], "regress_fine."), dev, **kw)
+        for r in (mid, fine):
+            if mode:
+                r.set_mode(mode)
         return mid, fine
 
     def timed(regs, rounds):
@@ -73,28 +79,53 @@ def main():
         ts = sorted(ts)
         med = ts[len(ts) // 2]
         say(f"{name}: n={n} x 2 levels  median {med:.2f} ms  min {ts[0]:.2f} ms  ({conv_flops(lay, n) / med / 1e9:.1f} TFLOP/s "
-            f"of exact-fp32 layer arithmetic, {len(ts)} calls)")
-        return med
+            f"of exact-fp32 layer arithmetic, {len(ts)} calls, max {ts[-1]:.2f} ms)")
+        return med, ts[0], ts[-1]
+
+    def differences(ra, rb):
+        """largest coordinate / score difference of two (mid, fine) handle pairs: the mid level on the proposals, the fine level
+        of both started from ra's mid matches (so that no trunc() of a mid coordinate that differs in its last bits picks another patch)"""
+        ma, mb = (ops.regress_batch(r[0], None, [a1], [a2], [props])[0] for r in (ra, rb))
+        start = ma["matches1"].clone()
+        fa, fb = (ops.regress_batch(r[1], None, [a1], [a2], [start])[0] for r in (ra, rb))
+        dc = max((ma["matches1"] - mb["matches1"]).abs().max().item(), (fa["matches1"] - fb["matches1"]).abs().max().item())
+        ds = max((ma["probs1"] - mb["probs1"]).abs().max().item(), (fa["probs1"] - fb["probs1"]).abs().max().item())
+        return dc, ds
+
+    def generic_pair(label, lay, ck=None, case=None):
+        """both generic modes of one configuration, alternating; -> their (median, min, max) and the largest output difference"""
+        regs = [handles(case, True, "generic", ck), handles(case, True, "generic_fp16x2", ck)]
+        dc, ds = differences(*regs)
+        timed(regs, warm)
+        t_g, t_h = timed(regs, niter)
+        r_g = report(f"{label} generic  ", lay, t_g)
+        r_h = report(f"{label} generic_fp16x2", lay, t_h)
+        say(f"{label} generic / generic_fp16x2 = {r_g[0] / r_h[0]:.2f}x (ranges {r_g[1]:.2f}-{r_g[2]:.2f} ms and {r_h[1]:.2f}-{r_h[2]:.2f} ms); "
+            f"largest difference of the two modes' outputs (mid, and fine from the same mid) {dc:.3g} px / {ds:.3g}")
+        return r_g, r_h
 
     say(f"device: {torch.cuda.get_device_name(0)}; pair {H}x{W}; WARMUP={warm} NITER={niter}")
-    tuned, generic = handles("R", False), handles("R", True)
-    for r in tuned:
-        r.set_mode("f32")
-    both = [tuned, generic]
-    outs = [ops.regress_batch(m, f, [a1], [a2], [props])[0] for m, f in both]
-    dc = (outs[0]["matches2"] - outs[1]["matches2"]).abs().max().item()
-    ds = (outs[0]["probs2"] - outs[1]["probs2"]).abs().max().item()
-    timed(both, warm)
-    t_tuned, t_gen = timed(both, niter)
+    four = [handles("R", False, "f32"), handles("R", False, "fp16x2"), handles("R", True, "generic"), handles("R", True, "generic_fp16x2")]
+    outs = [ops.regress_batch(m, f, [a1], [a2], [props])[0] for m, f in four]
+    timed(four, warm)
+    ts = timed(four, max(niter, 3))
     lay = ops.regressor_layout(None, None)
-    m_t = report("case R tuned f32", lay, t_tuned)
-    m_g = report("case R generic  ", lay, t_gen)
-    say(f"case R generic / tuned f32 = {m_g / m_t:.2f}x; largest difference of the fine outputs {dc:.3g} px / {ds:.3g}")
-    del tuned, generic, both
+    r_t = report("case R tuned f32", lay, ts[0])
+    r_t2 = report("case R tuned fp16x2", lay, ts[1])
+    r_g = report("case R generic  ", lay, ts[2])
+    r_h = report("case R generic_fp16x2", lay, ts[3])
+    dc, ds = (outs[0]["matches2"] - outs[2]["matches2"]).abs().max().item(), (outs[0]["probs2"] - outs[2]["probs2"]).abs().max().item()
+    say(f"case R generic / tuned f32 = {r_g[0] / r_t[0]:.2f}x; largest difference of the fine outputs {dc:.3g} px / {ds:.3g}")
+    dc, ds = differences(four[2], four[3])
+    say(f"case R generic / generic_fp16x2 = {r_g[0] / r_h[0]:.2f}x (ranges {r_g[1]:.2f}-{r_g[2]:.2f} ms and {r_h[1]:.2f}-{r_h[2]:.2f} ms; "
+        f"generic_fp16x2 / tuned fp16x2 = {r_h[0] / r_t2[0]:.2f}x); largest difference of the two modes' outputs (mid, and fine from the same mid) {dc:.3g} px / {ds:.3g}")
+    del four, outs
     for case in ("A", "C"):
-        regs = [handles(case, True)]
-        timed(regs, warm)
-        report(f"case {case} generic  ", ops.regressor_layout(rr.regressor_config(case), rr.CASES[case]["feat_idx"]), timed(regs, niter)[0])
+        generic_pair(f"case {case}", ops.regressor_layout(rr.regressor_config(case), rr.CASES[case]["feat_idx"]), case=case)
+    import bottleneck_reference as br  # noqa: E402
+    rc = synthetic.default_regressor_config(**br.SMALL_RC)
+    ck = synthetic.make_checkpoint(505, regressor_config=rc, feat_idx=[0, 1])
+    generic_pair("ResNet50 feat_idx [0, 1]", ops.regressor_layout(rc, [0, 1]), ck=ck)
     if "--out" in sys.argv:
         path = sys.argv[sys.argv.index("--out") + 1]
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
