@@ -86,10 +86,21 @@ int p2p_ncn_is_generic(const p2p_ncn *ncn);      /* 1 / 0; -1 for NULL */
  * Tile, strip walk and summation order are the default mode's: a result does not depend on the tile, the batch or the
  * workspace size in either mode.  Nothing is re-packed or uploaded on a change (the packed weights hold plane 0 already).
  * Mutual matching, match extraction, the scores and the operator entry points (p2p_correlation_batch, p2p_conv4d_*,
- * p2p_maxpool4d_batch) are not affected.  An unknown mode -> P2P_EINVAL; a generic handle -> P2P_EUNSUPPORTED (its kernels
- * are exact fp32); NULL -> P2P_EINVAL from the setter, -1 from the getter.                                              */
+ * p2p_maxpool4d_batch) are not affected.  An unknown mode -> P2P_EINVAL; P2P_COARSE_FP16 on a generic handle ->
+ * P2P_EUNSUPPORTED; NULL -> P2P_EINVAL from the setter, -1 from the getter.
+ * A generic handle (p2p_ncn_create_config) has two modes of its own.  0 is its default arithmetic: exact fp32 MFMA.
+ * P2P_COARSE_GENERIC_FP16X2 is opt-in and fp32-equivalent: every layer behind the first (more than one input channel) runs on
+ * the fp16 matrix cores with two fp16 planes per operand and three MFMA products -- the weights under one exact power of two
+ * per output channel, a layer's input under one power of two per PAIR (the largest magnitude the producing layer stored for
+ * that pair), fp32 accumulation in an order the configuration alone fixes; the first layer stays exact, so a single-layer
+ * stack computes the same bits in both modes.  A pair's result does not depend on the batch, its position or the workspace
+ * size; a non-finite value stays inside its own pair.  The planes are packed and uploaded on the first selection (a failure
+ * there -> P2P_ENOMEM / P2P_EHIP, the mode unchanged).  The mode needs a little more workspace: query
+ * p2p_coarse_workspace_bytes_for / p2p_neigh_consensus_workspace_bytes again after a mode change.  On a tuned handle the id
+ * is P2P_EUNSUPPORTED.  p2p_conv4d_* is not affected.                                                                      */
 #define P2P_COARSE_FP16X2 0
 #define P2P_COARSE_FP16   1
+#define P2P_COARSE_GENERIC_FP16X2 17
 int p2p_ncn_set_mode(p2p_ncn *ncn, int mode);
 int p2p_ncn_get_mode(const p2p_ncn *ncn);
 

@@ -96,6 +96,9 @@ p2p_ncn_set_mode = _sig("p2p_ncn_set_mode", ctypes.c_int, [ctypes.c_void_p, ctyp
 p2p_ncn_get_mode = _sig("p2p_ncn_get_mode", ctypes.c_int, [ctypes.c_void_p])
 # P2P_COARSE_FP16X2 (default, fp32-equivalent) / P2P_COARSE_FP16 (opt-in, one fp16 plane per operand: NOT fp32-equivalent)
 COARSE_MODES = {"fp16x2": 0, "fp16": 1}
+# a generic handle's own modes: 0 (default, exact fp32 MFMA) / P2P_COARSE_GENERIC_FP16X2 (opt-in, fp32-equivalent: every layer
+# behind the first on the fp16 matrix cores, two fp16 planes per operand)
+COARSE_MODES_GENERIC = {"generic": 0, "generic_fp16x2": 17}
 p2p_regressor_create = _sig("p2p_regressor_create", ctypes.c_int,
                             [ctypes.POINTER(RegressorParams), ctypes.POINTER(ctypes.c_void_p)])
 p2p_regressor_create_config = _sig("p2p_regressor_create_config", ctypes.c_int,

@@ -625,6 +625,7 @@ void launch_mm_apply(const float *X, int nA, int nB, const int *rkey, const int 
 
 // sections 4 (its shape-generic part), 5 and 6, and the stand-alone operators: no units of their own
 #include "consensus_generic.hip"
+#include "consensus_generic_h2.hip"
 #include "matches.hip"
 #include "score.hip"
 #include "operators.hip"

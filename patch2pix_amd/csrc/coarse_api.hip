@@ -11,7 +11,7 @@ struct CoarseWs {
     size_t fnA, fnB, P, Y, Y2, keys, act, total;   // byte offsets
 };
 // gen: the generic consensus net whose activation buffers the pair's block holds as well (null: a tuned handle, none)
-static CoarseWs coarse_ws(int C, int hA, int wA, int hB, int wB, int k, const NcGen *gen = nullptr) {
+static CoarseWs coarse_ws(int C, int hA, int wA, int hB, int wB, int k, const NcGen *gen = nullptr, int mode = 0) {
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t nA = (size_t)hA * wA, nB = (size_t)hB * wB;
     const size_t nAc = nA / (k * k), nBc = nB / (k * k);
@@ -24,7 +24,7 @@ static CoarseWs coarse_ws(int C, int hA, int wA, int hB, int wB, int k, const Nc
     w.Y2 = off; off += al(nAc * nBc * 4);
     w.keys = off; off += al((2 * (nAc + nBc) + 1) * 4);      // row / column maxima of both mutual matchings + max |X|
     w.act = off;
-    if (gen) off += nc_generic_ws_bytes(*gen, nAc * nBc);
+    if (gen) off += nc_generic_ws_bytes(*gen, nAc * nBc, mode);
     w.total = off;
     return w;
 }
@@ -65,8 +65,16 @@ extern "C" int p2p_ncn_set_tile(p2p_ncn *ncn, int ta, int tb, int tc) {
 
 extern "C" int p2p_ncn_set_mode(p2p_ncn *ncn, int mode) {
     P2P_REQUIRE(ncn, P2P_EINVAL, "p2p_ncn_set_mode: null handle");
-    P2P_REQUIRE(mode == P2P_COARSE_FP16X2 || mode == P2P_COARSE_FP16, P2P_EINVAL, "p2p_ncn_set_mode: unknown mode %d", mode);
-    P2P_REQUIRE(!ncn->gen, P2P_EUNSUPPORTED, "p2p_ncn_set_mode: a generic consensus handle runs exact fp32 kernels and has no modes");
+    P2P_REQUIRE(mode == P2P_COARSE_FP16X2 || mode == P2P_COARSE_FP16 || mode == P2P_COARSE_GENERIC_FP16X2, P2P_EINVAL,
+                "p2p_ncn_set_mode: unknown mode %d", mode);
+    if (mode == P2P_COARSE_GENERIC_FP16X2) {
+        P2P_REQUIRE(ncn->gen, P2P_EUNSUPPORTED, "p2p_ncn_set_mode: P2P_COARSE_GENERIC_FP16X2 is a mode of generic consensus handles");
+        const int st = nc_generic_ensure_h2(ncn->gen);      // packs and uploads the planes on the first selection
+        if (st != P2P_OK) return st;
+    }
+    // 0 is every handle's default arithmetic: exact fp32 for a generic one
+    P2P_REQUIRE(!ncn->gen || mode != P2P_COARSE_FP16, P2P_EUNSUPPORTED,
+                "p2p_ncn_set_mode: a generic consensus handle has no single-plane mode (0 or P2P_COARSE_GENERIC_FP16X2)");
     ncn->mode = mode;
     return P2P_OK;
 }
@@ -85,12 +93,12 @@ extern "C" size_t p2p_coarse_workspace_bytes(int channels, int hA, int wA, int h
 
 extern "C" size_t p2p_coarse_workspace_bytes_for(const p2p_ncn *ncn, int channels, int hA, int wA, int hB, int wB, int ksize) {
     if (!ncn || channels <= 0 || hA <= 0 || wA <= 0 || hB <= 0 || wB <= 0 || ksize < 1) return 0;
-    return coarse_ws(channels, hA, wA, hB, wB, ksize, ncn->gen).total;
+    return coarse_ws(channels, hA, wA, hB, wB, ksize, ncn->gen, ncn->mode).total;
 }
 
 extern "C" size_t p2p_neigh_consensus_workspace_bytes(const p2p_ncn *ncn, int hA, int wA, int hB, int wB) {
     if (!ncn || hA <= 0 || wA <= 0 || hB <= 0 || wB <= 0) return 0;
-    return ncn->gen ? nc_generic_ws_bytes(*ncn->gen, (size_t)hA * wA * hB * wB) : sizeof(int);
+    return ncn->gen ? nc_generic_ws_bytes(*ncn->gen, (size_t)hA * wA * hB * wB, ncn->mode) : sizeof(int);
 }
 
 extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, int batch, int C, int hA, int wA, int hB,
@@ -108,7 +116,7 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
     // ncn = 1 with a 64-byte workspace and expects the workspace error, as before generic handles existed).
     const size_t ws_any = coarse_ws(C, hA, wA, hB, wB, ksize).total;
     P2P_REQUIRE(workspace_bytes >= ws_any, P2P_ENOMEM, "p2p_coarse_forward: workspace %zu < %zu bytes (one pair)", workspace_bytes, ws_any);
-    const CoarseWs ws = coarse_ws(C, hA, wA, hB, wB, ksize, ncn->gen);
+    const CoarseWs ws = coarse_ws(C, hA, wA, hB, wB, ksize, ncn->gen, ncn->mode);
     P2P_REQUIRE(workspace_bytes >= ws.total, P2P_ENOMEM, "p2p_coarse_forward: workspace %zu < %zu bytes (one pair)", workspace_bytes,
                 ws.total);
     P2P_REQUIRE(!ncn->gen || ((uintptr_t)workspace & 15) == 0, P2P_EINVAL,
@@ -140,7 +148,7 @@ extern "C" int p2p_coarse_forward_batch(const float *featA, const float *featB, 
         // first mutual matching, in place on the pooled volume (+ max |X| for the consensus kernel's operand scale)
         launch_mm_apply(P, nAc, nBc, rkey1, ckey1, P, sWs, sWs, sWs, xmax, nullptr, nz, stream);
         if (ncn->gen) {   // a generic stack: layer by layer, the sum of its branches in Y
-            st = launch_nc_generic(*ncn->gen, P, sWs, Y, sWs, (float *)(base + ws.act), sWs, (int)nz, d0, d1, d2, d3, stream);
+            st = launch_nc_generic(*ncn->gen, ncn->mode, P, sWs, Y, sWs, (float *)(base + ws.act), sWs, (int)nz, d0, d1, d2, d3, stream);
             Y2 = nullptr;
         } else {   // both consensus layers, both branches: relu(.) of the direct branch into Y, of the transposed one into Y2
             st = launch_nc_fused(P, Y, Y2, sWs, (int)nz, d0, d1, d2, d3, ncn->wfused.dev<unsigned char>(), ncn->b2, xmax, sWs, ncn->tile, planes, stream);
@@ -165,12 +173,12 @@ extern "C" int p2p_neigh_consensus_batch(const float *x, int batch, int hA, int 
     P2P_REQUIRE(x && ncn && y_out && workspace, P2P_EINVAL, "p2p_neigh_consensus: null argument");
     P2P_REQUIRE(batch >= 1 && batch <= 65535 && hA > 0 && wA > 0 && hB > 0 && wB > 0, P2P_EINVAL, "p2p_neigh_consensus: bad sizes");
     if (ncn->gen) {
-        const size_t cells = (size_t)hA * wA * hB * wB, per = nc_generic_ws_bytes(*ncn->gen, cells);
+        const size_t cells = (size_t)hA * wA * hB * wB, per = nc_generic_ws_bytes(*ncn->gen, cells, ncn->mode);
         P2P_REQUIRE(workspace_bytes >= per, P2P_ENOMEM, "p2p_neigh_consensus: workspace %zu < %zu bytes (one volume)", workspace_bytes, per);
         P2P_REQUIRE(((uintptr_t)workspace & 15) == 0, P2P_EINVAL, "p2p_neigh_consensus: the workspace of a generic handle must be 16-byte aligned");
         const int per_launch = (int)std::min<size_t>(batch, workspace_bytes / per);      // volumes the workspace holds at once
         for (int z0 = 0; z0 < batch; z0 += per_launch) {
-            const int st = launch_nc_generic(*ncn->gen, x + (size_t)z0 * cells, cells, y_out + (size_t)z0 * cells, cells, (float *)workspace,
+            const int st = launch_nc_generic(*ncn->gen, ncn->mode, x + (size_t)z0 * cells, cells, y_out + (size_t)z0 * cells, cells, (float *)workspace,
                                              per / sizeof(float), std::min(per_launch, batch - z0), hA, wA, hB, wB, stream);
             if (st != P2P_OK) return st;
         }

@@ -64,8 +64,10 @@ int launch_absmax(const float *x, size_t n, size_t stride, int pairs, int *out, 
 // ---- consensus_generic.hip: any other stack, one launch per layer and branch (NcGen: the handle's layers, defined there) ----
 int nc_generic_create(const p2p_ncn_config *cfg, const p2p_ncn_tensors *t, NcGen **out);
 void nc_generic_destroy(NcGen *g);
-size_t nc_generic_ws_bytes(const NcGen &g, size_t cells);
-int launch_nc_generic(const NcGen &g, const float *X, size_t s_x, float *Y, size_t s_y, float *act, size_t s_act, int pairs,
+// mode: the handle's (0 or P2P_COARSE_GENERIC_FP16X2, consensus_generic_h2.hip; its planes: nc_generic_ensure_h2, once)
+size_t nc_generic_ws_bytes(const NcGen &g, size_t cells, int mode);
+int nc_generic_ensure_h2(NcGen *g);
+int launch_nc_generic(const NcGen &g, int mode, const float *X, size_t s_x, float *Y, size_t s_y, float *act, size_t s_act, int pairs,
                       int d0, int d1, int d2, int d3, hipStream_t stream);
 
 // one stand-alone Conv4d layer (p2p_conv4d_*): the PLANAR form of the generic kernel (Conv4dLayer: defined there)
@@ -103,7 +105,8 @@ struct p2p_ncn {
     p2p::DeviceBlob wfused;  // both layers, both branches as fp16x2 MFMA fragments (consensus.hip)
     int tile[3];             // forced (ta, tb, tc) of the fused kernel, 0 = automatic (p2p_ncn_set_tile: tests and sweeps)
     p2p::NcGen *gen;         // a generic handle (p2p_ncn_create_config): its layers; the fields above are unused then
-    int mode = 0;            // P2P_COARSE_FP16X2 / P2P_COARSE_FP16 (p2p_ncn_set_mode): planes per operand of the matrix-core kernels
+    int mode = 0;            // P2P_COARSE_FP16X2 / P2P_COARSE_FP16 (p2p_ncn_set_mode): planes per operand of the matrix-core kernels;
+                             // a generic handle: 0 (exact fp32) or P2P_COARSE_GENERIC_FP16X2
     ~p2p_ncn() { p2p::nc_generic_destroy(gen); }
 };
 

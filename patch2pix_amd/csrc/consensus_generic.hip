@@ -40,10 +40,21 @@ struct NcGenLayer {
     const float *bias;       // [16], zero past co
 };
 
+// a layer behind the first in mode P2P_COARSE_GENERIC_FP16X2 (consensus_generic_h2.hip)
+struct NcH2Layer {
+    const unsigned char *w[2];   // fp16 plane fragments of the direct / transposed branch (pack_conv4d_planes, host_pack.h)
+    const float *wscale;         // [16] 2^-texp of the output channel
+    int nh, nstep, sub, lds_bytes;
+};
+constexpr int NCH2_WORDS = 2 * NCG_MAX_LAYERS;      // max words of a pair: word br * NCG_MAX_LAYERS + i = max |output of layer i|
+
 struct NcGen {
     int n_layers, symmetric, cpmax;
     NcGenLayer layer[NCG_MAX_LAYERS];
     DeviceBlob mem;          // one device allocation: every layer's fragments and biases
+    std::vector<float> w_host[NCG_MAX_LAYERS];      // the stored weights of the layers behind the first, for the planes
+    DeviceBlob mem_h2;       // the fp16x2 planes, packed and uploaded on the mode's first selection
+    NcH2Layer h2[NCG_MAX_LAYERS];
 };
 
 struct NcGenArgs {
@@ -57,7 +68,13 @@ struct NcGenArgs {
     int add;                 // last layer of the transposed branch: out += result
     int ci;                  // PLANAR only: the real input channels (channel ch of a cell sits ch * cells floats further on)
     size_t cells;            // PLANAR only: cells of the volume = floats between two channel planes
+    int *amax;               // P2P_COARSE_GENERIC_FP16X2 (consensus_generic_h2.hip): the pair's max |stored value| is reduced into
+    size_t s_amax;           // amax[pair * s_amax] (float bits, zeroed by the launcher); null: nothing is reduced
 };
+
+int launch_nc_generic_h2_zero(int *words, size_t s_words, int pairs, hipStream_t stream);
+int launch_nc_generic_h2_layer(const NcGenArgs &a, const NcGenLayer &L, const NcH2Layer &H, int br, const int *amax_in, int *amax_out,
+                               int pairs, hipStream_t stream);
 
 __device__ __forceinline__ int ncg_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
@@ -144,13 +161,14 @@ __global__ __launch_bounds__(256) void nc_generic_kernel(NcGenArgs a) {
         for (int S = 0; S < a.nsteps; ++S) step(S, acc);
     }
     // accumulator register r = cell dt0 + 4 kb + r of the row, column l15 = output channel
-    if (l15 >= a.cpo) return;
+    const bool col = l15 < a.cpo;
     const float bias = a.bias[l15];
     const size_t row0 = (size_t)((aa * a.d1 + b) * a.d2 + c) * a.d3;
+    float amax = 0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int od = dt0 + 4 * kb + r;
-        if (od >= a.d3) continue;
+        if (!col || od >= a.d3) continue;
         if constexpr (PLANAR) {
             out[(size_t)l15 * a.cells + row0 + od] = acc[r] + bias;
             continue;
@@ -158,6 +176,13 @@ __global__ __launch_bounds__(256) void nc_generic_kernel(NcGenArgs a) {
         float *dst = out + (row0 + od) * a.cpo + l15;
         const float v = fmaxf(acc[r] + bias, 0.f);
         *dst = a.add ? *dst + v : v;
+        amax = fmaxf(amax, v);
+    }
+    if constexpr (!PLANAR) {
+        if (!a.amax) return;                  // (the whole wave)
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) amax = fmaxf(amax, __shfl_xor(amax, m));
+        if (lane == 0) atomicMax(a.amax + (size_t)blockIdx.z * a.s_amax, __float_as_int(amax));
     }
 }
 
@@ -224,6 +249,7 @@ int nc_generic_create(const p2p_ncn_config *cfg, const p2p_ncn_tensors *t, NcGen
     for (int i = 0; i < g->n_layers; ++i) {
         const NcGenLayer &L = g->layer[i];
         for (int br = 0; br < nbr; ++br) gen_nc_pack(t->w[i], L, i == 0, br, &h[o_w[i][br]]);
+        if (i) g->w_host[i].assign(t->w[i], t->w[i] + (size_t)L.k * L.k * L.k * L.k * L.co * L.ci);
         for (int q = 0; q < L.co; ++q) h[o_b[i] + q] = t->b[i][q];
     }
     const int st = g->mem.upload("p2p_ncn_create_config: the packed consensus net");
@@ -245,12 +271,14 @@ int nc_generic_create(const p2p_ncn_config *cfg, const p2p_ncn_tensors *t, NcGen
 void nc_generic_destroy(NcGen *g) { delete g; }      // (NcGen is complete in this unit only)
 
 // scratch of one volume: the two activation buffers layers alternate between (a single layer needs none: one block)
-size_t nc_generic_ws_bytes(const NcGen &g, size_t cells) {
-    return std::max<size_t>(256, (2 * cells * g.cpmax * sizeof(float) + 255) & ~size_t(255));
+// P2P_COARSE_GENERIC_FP16X2 adds one block of max words behind them
+size_t nc_generic_ws_bytes(const NcGen &g, size_t cells, int mode) {
+    const size_t act = std::max<size_t>(256, (2 * cells * g.cpmax * sizeof(float) + 255) & ~size_t(255));
+    return act + (mode == P2P_COARSE_GENERIC_FP16X2 && g.n_layers > 1 ? 256 : 0);
 }
 
 // NeighConsensus.forward for `pairs` volumes: X / Y / act of pair z sit z * s_x / s_y / s_act floats further on
-int launch_nc_generic(const NcGen &g, const float *X, size_t s_x, float *Y, size_t s_y, float *act, size_t s_act, int pairs,
+int launch_nc_generic(const NcGen &g, int mode, const float *X, size_t s_x, float *Y, size_t s_y, float *act, size_t s_act, int pairs,
                       int d0, int d1, int d2, int d3, hipStream_t stream) {
     // cell offsets are computed in 32 bits
     P2P_REQUIRE((unsigned long long)d0 * d1 * d2 * d3 < (1ull << 31), P2P_EUNSUPPORTED,
@@ -263,6 +291,14 @@ int launch_nc_generic(const NcGen &g, const float *X, size_t s_x, float *Y, size
     P2P_REQUIRE(tiles < (1ll << 31) - 4, P2P_EUNSUPPORTED, "consensus volume: %lld row tiles in one launch", tiles);
     a.tiles = (int)tiles;
     const dim3 grid((unsigned)((tiles + 3) / 4), 1, (unsigned)pairs);
+    const bool h2 = mode == P2P_COARSE_GENERIC_FP16X2 && g.n_layers > 1;      // (a single layer is the exact first layer)
+    int *words = h2 ? (int *)act + nc_generic_ws_bytes(g, cells, 0) / sizeof(int) : nullptr;
+    if (h2) {
+        P2P_REQUIRE(g.mem_h2.uploaded(), P2P_EINVAL, "consensus net: the planes of P2P_COARSE_GENERIC_FP16X2 were never packed");
+        const int st = launch_nc_generic_h2_zero(words, s_act, pairs, stream);
+        if (st != P2P_OK) return st;
+        a.s_amax = s_act;
+    }
     for (int br = 0; br < (g.symmetric ? 2 : 1); ++br)
         for (int i = 0; i < g.n_layers; ++i) {
             const NcGenLayer &L = g.layer[i];
@@ -272,6 +308,12 @@ int launch_nc_generic(const NcGen &g, const float *X, size_t s_x, float *Y, size
             a.w = L.w[br]; a.bias = L.bias;
             a.k = L.k; a.cpi = L.cpi; a.cpo = L.cpo; a.nsteps = L.nsteps;
             a.add = last && br == 1;
+            a.amax = h2 && !last ? words + br * NCG_MAX_LAYERS + i : nullptr;
+            if (h2 && i) {
+                const int st = launch_nc_generic_h2_layer(a, L, g.h2[i], br, words + br * NCG_MAX_LAYERS + i - 1, a.amax, pairs, stream);
+                if (st != P2P_OK) return st;
+                continue;
+            }
             if (i == 0) hipLaunchKernelGGL((nc_generic_kernel<true, false>), grid, dim3(256), 0, stream, a);
             else hipLaunchKernelGGL((nc_generic_kernel<false, false>), grid, dim3(256), 0, stream, a);
             const int st = check_launch("nc_generic_kernel");

@@ -143,6 +143,44 @@ static inline void pack_conv_planes(const float *w, int co, int cin, int taps, i
                     }
 }
 
+// Conv4d weight in the stored layout [k(da)][co][ci][k(db)][k(dc)][k(dd)] (co, ci <= 16) -> the two-plane fp16 B fragments of
+// v_mfma_f32_16x16x32_f16 in the order consensus_generic_h2.hip streams them: per da slice, steps of 4 / nh taps of the slice's
+// k^3 in the order (db, dc, dd), nh = 1 (8 staged input channels) or 2 (16):
+//   out[(((da * nstep + step) * 2 + plane) * 64 + lane) * 8 + i] = plane (0 high, 1 low) of
+//   W[n = lane & 15][ch = 8 ((lane >> 4) % nh) + i][da][tap = (4 / nh) step + (lane >> 4) / nh] * 2^texp[n],
+//   texp[n] = pow2_exponent_to(max |W[n]|, 12), zeros past co, past ci and past the slice's last tap.
+// Branch 1 is the transposed branch of symmetric_mode: in the volume's own coordinates the weight of offset (da, db, dc, dd) is
+// W[dc][dd][da][db] (the exponents are those of branch 0: the same values).
+static inline size_t conv4d_planes_steps(int k, int nh) { return (size_t)(k * k * k + 4 / nh - 1) / (4 / nh); }
+static inline size_t conv4d_planes_halfs(int k, int nh) { return (size_t)k * conv4d_planes_steps(k, nh) * 1024; }
+static inline void pack_conv4d_planes(const float *w, int k, int co, int ci, int nh, int br, uint16_t *out, int *texp) {
+    const int ntap = k * k * k, tpm = 4 / nh, nstep = (int)conv4d_planes_steps(k, nh);
+    auto W = [&](int o, int i, int da, int db, int dc, int dd) {
+        return w[((((size_t)(da * co + o) * ci + i) * k + db) * k + dc) * k + dd];
+    };
+    for (int n = 0; n < co; ++n) {
+        double mx = 0.0;
+        for (int i = 0; i < ci; ++i)
+            for (int da = 0; da < k; ++da)
+                for (int t = 0; t < ntap; ++t) mx = std::max(mx, (double)std::fabs(W(n, i, da, t / (k * k), (t / k) % k, t % k)));
+        texp[n] = pow2_exponent_to(mx, 12);
+    }
+    for (int da = 0; da < k; ++da)
+        for (int s = 0; s < nstep; ++s)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int i = 0; i < 8; ++i) {
+                    const int n = lane & 15, g = lane >> 4, tap = tpm * s + g / nh, ch = 8 * (g % nh) + i;
+                    uint16_t hi = 0, lo = 0;
+                    if (n < co && ch < ci && tap < ntap) {
+                        const int db = tap / (k * k), dc = (tap / k) % k, dd = tap % k;
+                        split_fp16_planes(std::ldexp(br ? W(n, ch, dc, dd, da, db) : W(n, ch, da, db, dc, dd), texp[n]), &hi, &lo);
+                    }
+                    const size_t at = (((size_t)da * nstep + s) * 2 * 64 + lane) * 8 + i;
+                    out[at] = hi;
+                    out[at + 512] = lo;
+                }
+}
+
 // ---- launchers ------------------------------------------------------------------------------------------------------------
 // What a launcher does before a kernel whose dynamic LDS allocation exceeds the default limit: ask for the current device (once
 // per launch) and, on that device's first launch, raise the limit of each kernel; `once` is set only after all of them succeeded.

@@ -211,20 +211,26 @@ class Patch2Pix(nn.Module):
         """'fp16x2' (default, fp32-equivalent) or the opt-in 'fp16' for the matrix-core kernels of the coarse stage (one fp16
         plane per operand, one MFMA product per product: NOT fp32-equivalent, see ops.NcnWeights.set_mode).  The choice belongs
         to the model: it is applied to the packed consensus handle now and again whenever the weights are re-packed
-        (load_state_dict, init_weights_).  A model with a generic consensus stack raises NotImplementedError."""
-        ops.coarse_mode_id(mode)                                    # ValueError for an unknown name, before anything changes
-        if self._ncn_layout != ops.RELEASED_NCN_LAYOUT:
-            raise NotImplementedError("set_coarse_mode: a generic consensus stack runs exact fp32 kernels and has no modes")
+        (load_state_dict, init_weights_).  A model with a generic consensus stack (any but the released one) accepts 'generic'
+        (default, exact fp32 MFMA) and the opt-in 'generic_fp16x2' (fp32-equivalent, ops.NcnWeights.set_mode) instead.  A name of
+        the other kind raises NotImplementedError, an unknown one ValueError -- both before anything changes."""
+        generic = self._ncn_layout != ops.RELEASED_NCN_LAYOUT
+        names = ops._lib.COARSE_MODES_GENERIC if generic else ops._lib.COARSE_MODES
+        if not isinstance(mode, str) or (mode not in ops._lib.COARSE_MODES and mode not in ops._lib.COARSE_MODES_GENERIC):
+            raise ValueError(f"unknown coarse mode {mode!r}: one of {sorted(names)}")
+        if mode not in names:
+            raise NotImplementedError(f"set_coarse_mode: {mode!r} is no mode of this model's consensus stack (one of {sorted(names)})")
         self._coarse_mode = mode
         if self._packed is not None:
             self._packed[0].set_mode(mode)
 
     @property
     def coarse_mode(self):
-        """The mode `set_coarse_mode` chose, or the one new handles start in (P2P_COARSE_MODE, else 'fp16x2'); 'fp16x2' for a
-        generic consensus stack."""
+        """The mode `set_coarse_mode` chose, or the one new handles start in (P2P_COARSE_MODE, else 'fp16x2'); for a generic
+        consensus stack the chosen generic name, P2P_COARSE_GENERIC_MODE=generic_fp16x2 when set, else 'fp16x2' as before."""
         if self._ncn_layout != ops.RELEASED_NCN_LAYOUT:
-            return "fp16x2"
+            start = ops.default_coarse_generic_mode()
+            return getattr(self, "_coarse_mode", None) or (start if start != "generic" else "fp16x2")
         return getattr(self, "_coarse_mode", None) or ops.default_coarse_mode()
 
     def _fine_mode_names(self):

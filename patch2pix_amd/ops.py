@@ -96,6 +96,12 @@ def default_coarse_mode():
     return os.environ.get("P2P_COARSE_MODE") or "fp16x2"
 
 
+def default_coarse_generic_mode():
+    """The mode new generic NcnWeights handles start in: P2P_COARSE_GENERIC_MODE=generic|generic_fp16x2 (read here, not in the
+    library); P2P_COARSE_MODE applies to tuned handles only."""
+    return os.environ.get("P2P_COARSE_GENERIC_MODE") or "generic"
+
+
 class NcnWeights:
     """Device-resident NeighConsensus filters (reference networks/ncn/model.py:124-143).  The constructor takes the released
     stack's four tensors (the tuned kernel); `from_state_dict` takes any stack within `ncn_layout`'s limits."""
@@ -133,6 +139,8 @@ class NcnWeights:
         with torch.cuda.device(device):
             _lib.check(_lib.p2p_ncn_create_config(ctypes.byref(c), ctypes.byref(t), ctypes.byref(self.handle)), "p2p_ncn_create_config")
         self.device, self.layout, self.generic = torch.device(device), lay, True
+        if default_coarse_generic_mode() != "generic":
+            self.set_mode(default_coarse_generic_mode())
         return self
 
     def set_tile(self, ta=0, tb=0, tc=0):
@@ -145,16 +153,25 @@ class NcnWeights:
         """'fp16x2' (default: fp32-equivalent, two fp16 planes per operand, 3 MFMA products) or the opt-in 'fp16': the matrix-core
         kernels of every coarse-stage call with this handle (feature preparation, correlation + pooling, the fused consensus
         kernel) run with ONE fp16 plane per operand and one MFMA product -- relative operand rounding 2^-11, NOT
-        fp32-equivalent ("Single-plane mode of the coarse stage").  Nothing is packed or uploaded.  A
-        generic handle (exact fp32 kernels) has no modes: NotImplementedError."""
-        mid = coarse_mode_id(mode)
-        if self.generic:
-            raise NotImplementedError("set_mode: a generic consensus handle runs exact fp32 kernels and has no modes")
-        _lib.check(_lib.p2p_ncn_set_mode(self.handle, mid), "p2p_ncn_set_mode")
+        fp32-equivalent ("Single-plane mode of the coarse stage").  Nothing is packed or uploaded.
+        A generic handle has names of its own: 'generic' (default, exact fp32 MFMA) and the opt-in 'generic_fp16x2' (every layer
+        behind the first on the fp16 matrix cores, two fp16 planes per operand, three MFMA products: fp32-equivalent; the planes are
+        packed and uploaded on the first selection; DESIGN.md section 4, "fp16x2 mode of the generic consensus net").  A name of the
+        other kind of handle raises NotImplementedError, an unknown one ValueError, both before the library is asked."""
+        names = _lib.COARSE_MODES_GENERIC if self.generic else _lib.COARSE_MODES
+        if not isinstance(mode, str) or (mode not in _lib.COARSE_MODES and mode not in _lib.COARSE_MODES_GENERIC):
+            raise ValueError(f"unknown coarse mode {mode!r}: one of {sorted(names)}")
+        if mode not in names:
+            raise NotImplementedError(f"set_mode: {mode!r} is no mode of a {'generic' if self.generic else 'tuned'} consensus handle "
+                                      f"(one of {sorted(names)})")
+        with torch.cuda.device(self.device):                        # (the first selection of 'generic_fp16x2' uploads)
+            _lib.check(_lib.p2p_ncn_set_mode(self.handle, names[mode]), "p2p_ncn_set_mode")
 
     @property
     def mode(self):
         mid = _lib.p2p_ncn_get_mode(self.handle)
+        if self.generic and mid:
+            return next(k for k, v in _lib.COARSE_MODES_GENERIC.items() if v == mid)
         return next(k for k, v in _lib.COARSE_MODES.items() if v == mid)
 
     def __del__(self):
